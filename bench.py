@@ -14,12 +14,21 @@ under torch.distributed.run the ranks come from the environment and must
 number exactly --gpus.  Ranks never share a device unless
 --allow-shared-device (a rehearsal on a smaller box) says so.
 
-Besides the headline encode, the line's extras time, in the same process:
+A plain run does what the headline needs and no more: set up, warm up, time
+the K steps, write the outputs if --dump-outputs is given, print the line
+(extras empty, no CPU baseline).
+
+With --full the line's extras also time, in the same process:
 config 3 (reconstruct with 1-4 lost data shards), config 4 (RS(8,4) encode +
 fused HighwayHash-256 digests, the PUT path's kernel, encode.rs:601-628),
 config 5's per-GPU share (RS(16,4) encode, S = 65536, 8192 stripes) and the
 GET / heal / bitrot_verify engines — each with its kernel time, algorithmic
-bytes and roofline fraction.
+bytes and roofline fraction — then the RS(12,4) and host-memory extras and the
+CPU baseline (the --no-* options trim a --full run).
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy
+files (dump_outputs): the stripes are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -51,6 +60,12 @@ def parse(argv=None):
     ap.add_argument("--total-batch", type=int, default=0,
                     help="stripes over ALL GPUs, split evenly (strong scaling, BASELINE config 5)")
     ap.add_argument("--digests", action="store_true", help="fused HH256S digests (config 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the extras (reconstruct, config 4 / 5, engines, RS(12,4), "
+                         "host path) and the CPU baseline; off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, a seeded sample, "
+                         "under 64 MB in all; rank 0's share)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-stripes", type=int, default=256)
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -250,6 +265,62 @@ def random_stripes(dev, k, m, S, n, seed):
         s1 = min(n, s0 + step)
         st[s0:s1, :k] = torch.randint(0, 256, (s1 - s0, k, S), dtype=torch.uint8, device=dev, generator=g)
     return st
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: every file together, as float32
+DUMP_SEED = 5150
+
+
+def dump_plan(k, m, S, n, digests, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+    """What --dump-outputs keeps of one encode pass over (n, k+m, S) stripes,
+    the same for every run with the same geometry: {file name: (stripe
+    indices, byte columns or None for a whole row)}.  The parity is 2 GiB on
+    the default line, so the dump is a seeded sample of it in float32 elements
+    (4 bytes each): at most half the budget for the whole parity of a few
+    stripes ("parity_stripes"), a quarter for a few byte columns of every
+    stripe's parity, or of as many stripes as fit ("parity_columns"), and an
+    eighth for the fused digests of as many stripes as fit ("digests")."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    perm = rng.permutation(n)
+    budget = max_bytes // 4 - 3 * 64  # elements, less the three .npy headers
+    plan = {}
+    ns = min(n, (budget // 2) // (m * S))
+    if ns:
+        plan["parity_stripes"] = (np.sort(perm[:ns]), None)
+    nr = min(n, (budget // 4) // m)
+    nc = min(S, (budget // 4) // (nr * m))
+    plan["parity_columns"] = (np.sort(perm[:nr]), np.sort(rng.permutation(S)[:nc]))
+    if digests:
+        nd = min(n, (budget // 8) // ((k + m) * 32))
+        if nd:
+            plan["digests"] = (np.sort(perm[:nd]), None)
+    return plan
+
+
+def dump_outputs(out_dir, stripes, digests, k, m):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step — the parity shards the encode wrote into the stripes (and the
+    digests of --digests) — sampled by dump_plan, gathered on the device and
+    written as float32 out_dir/<name>.npy."""
+    import numpy as np
+    import torch
+    n, t, S = stripes.shape
+    dev = stripes.device
+    os.makedirs(out_dir, exist_ok=True)
+
+    def index(a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+    shard = torch.arange(k, t, device=dev)
+    for name, (rows, cols) in dump_plan(k, m, S, n, digests is not None).items():
+        if name == "digests":
+            got = digests[index(rows)]
+        elif cols is None:
+            got = stripes[index(rows), k:]
+        else:
+            got = stripes[index(rows)[:, None, None], shard[None, :, None], index(cols)[None, None, :]]
+        np.save(os.path.join(out_dir, name + ".npy"), got.cpu().numpy().astype(np.float32))
 
 
 PMC_TRAFFIC = os.path.join(ROOT, "tools", "pmc_traffic.json")
@@ -918,8 +989,11 @@ def main(argv=None):
     alg_bytes = n * (k + m) * S + (n * (k + m) * 32 if a.digests else 0)
     achieved = alg_bytes / (avg_ms * 1e-3) / 1e9
 
+    if a.dump_outputs and rank == 0:  # before the extras: config 3 rebuilds shards of this buffer
+        dump_outputs(a.dump_outputs, stripes, digests, k, m)
+
     extras = {}
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         # config 3: reconstruct with 1-4 missing data shards (same buffer)
         for miss in ((0,), (0, 3), (0, 3, 5), (0, 3, 5, 7)):
             present = [i not in miss for i in range(k + m)]
@@ -957,7 +1031,7 @@ def main(argv=None):
     traffic = pmc_traffic(k, m, S, n, a.digests)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(k, m, S, min(a.cpu_sample_stripes, n), a.cpu_threads or usable_cpus())
 
     if rank == 0:

@@ -98,8 +98,8 @@ def test_bench_self_launch_two_ranks_rehearsal(gpu):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--allow-shared-device", "--batch", "256",
-           "--steps", "2", "--warmup", "1", "--warm-seconds", "0", "--no-cpu-baseline", "--no-engines",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--allow-shared-device", "--full",
+           "--batch", "256", "--steps", "2", "--warmup", "1", "--warm-seconds", "0", "--no-cpu-baseline", "--no-engines",
            "--config4-batch", "256", "--config5-total", "1001"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=150)
     assert p.returncode == 0, p.stderr[-2000:]

@@ -192,16 +192,16 @@ def test_pmc_traffic_sources_are_committed_counters():
     (KiB, the microarch guide's gfx950 correction) recomputed from those
     CSVs."""
     import json
-    import subprocess
     import tools.pmc_traffic as P
     data = json.load(open(os.path.join(ROOT, "tools", "pmc_traffic.json")))
-    tracked = set(subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True,
-                                 check=True).stdout.split())
+    # the tree may be an export without its history: a committed file is one
+    # that is there, under profiles/ (no build or run writes into it)
     assert data
     for key, v in data.items():
         src = v["source"]
+        assert src.startswith("profiles/") and ".." not in src.split("/"), (key, src)
         for f in ("meta.json", "FETCH_SIZE/run_counter_collection.csv", "WRITE_SIZE/run_counter_collection.csv"):
-            assert f"{src}/{f}" in tracked, (key, f)
+            assert os.path.isfile(os.path.join(ROOT, src, f)), (key, f)
         k2, again = P.entry(os.path.join(ROOT, src))
         assert k2 == key and again["bytes_per_launch"] == v["bytes_per_launch"], key
 
@@ -257,3 +257,39 @@ def test_host_path_plan():
     assert bench.link_bound_ms(10e9, 50e9, 50.0, 25.0) == pytest.approx(2000.0)
     a = bench.parse([])
     assert a.host_path_blocks == 1024 and not a.no_host_path
+
+
+def test_plain_run_is_the_headline_alone():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline
+    only; the extras and the CPU baseline wait for --full (where the --no-*
+    options still trim them), and --dump-outputs names a directory."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "out", "--no-engines"])
+    assert a.full and a.dump_outputs == "out" and a.no_engines and not a.no_extras
+
+
+@pytest.mark.parametrize("k,m,S,n,digests", [(8, 4, 131072, 4096, False), (8, 4, 131072, 4096, True),
+                                             (16, 4, 65536, 8192, True), (12, 4, 87382, 3, True),
+                                             (8, 4, 2097152, 4096, False), (2, 1, 512, 6000000, True)])
+def test_dump_plan_is_seeded_and_bounded(k, m, S, n, digests):
+    """--dump-outputs keeps the same sample for the same geometry, every index
+    inside the batch, distinct and ascending, and under 64 MB of float32 in
+    all, headers included; a batch that fits is kept whole."""
+    import numpy as np
+    plan = bench.dump_plan(k, m, S, n, digests)
+    again = bench.dump_plan(k, m, S, n, digests)
+    assert plan.keys() == again.keys() and ("digests" in plan) == digests and "parity_columns" in plan
+    total = 0
+    for name, (rows, cols) in plan.items():
+        assert np.array_equal(rows, again[name][0])
+        assert len(rows) and rows[0] >= 0 and rows[-1] < n and (np.diff(rows) > 0).all()
+        width = (k + m) * 32 if name == "digests" else m * S
+        if cols is not None:
+            assert np.array_equal(cols, again[name][1])
+            assert len(cols) and cols[0] >= 0 and cols[-1] < S and (np.diff(cols) > 0).all()
+            width = m * len(cols)
+        total += 4 * len(rows) * width + 128
+    assert total <= 64 * 1000 * 1000
+    if n == 3:
+        assert all(len(rows) == 3 for rows, _ in plan.values()) and len(plan["parity_columns"][1]) == S
