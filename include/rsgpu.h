@@ -337,6 +337,57 @@ int rsg_encode_batch_host_submit(rsg_ctx *ctx, int k, int m, size_t shard_len, s
 int rsg_poll(rsg_ctx *ctx, uint64_t ticket, int *done);
 int rsg_wait(rsg_ctx *ctx, uint64_t ticket);
 
+/* ---- mixed-length batch: n unrelated stripes, each with its own shard length ----
+ * The batched form of the small-object path, encode_inline_shards_with_size_hint
+ * (encode.rs:601-628), which encodes one body of whatever size the client sent,
+ * and of the short last block of every object (encode_buffer's ceil(len / k)
+ * shards, erasure.rs:848-887): parity and all k+m bitrot digests of n blocks
+ * of different lengths in one launch.
+ * Stripe j (h_desc[j], a host array the call does not keep): data shard c is
+ * at data + data_off + c*shard_len (k shards back to back, as encode_buffer
+ * lays them out), parity shard r is written at parity + parity_off +
+ * r*shard_len, the k+m digests at digests + j*(k+m)*32 (caller order; NULL or
+ * algo NONE: parity only).  Any shard length up to 0xffffffff and any
+ * alignment; shard_len == 0 touches no memory and its digests are those of
+ * the empty message.  The descriptors must list stripes in ascending,
+ * disjoint order: data ranges [data_off, +k*shard_len) strictly ascending,
+ * parity ranges [parity_off, +m*shard_len) likewise, and no parity range may
+ * meet a data range or another parity range when the two arenas alias
+ * (parity == data with parity_off = data_off + k*shard_len is the a3 layout
+ * and is valid); anything else, a NULL pointer or an unknown algo is
+ * RSG_ERR_INVALID_ARG with nothing written.  Geometry errors as
+ * rsg_check_geometry; n == 0 is RSG_OK.
+ * One launch for k <= 16 with m = 1..4 (the fused encode + hash kernels'
+ * range); m == 0 (digests only), m > 4 and k > 16 give the same results
+ * through the per-length kernels, a few launches per stripe.
+ *
+ * rsg_encode_mixed_dev: device arenas, asynchronous on `stream` like
+ * rsg_encode_batch_dev.
+ *
+ * rsg_encode_mixed_host / _submit: host arenas, pipelined over the host-batch
+ * stream/staging slots with the same tickets (rsg_poll / rsg_wait) and the
+ * same contract as rsg_encode_batch_host_submit (a failed submit drains what
+ * it queued).  Consecutive stripes are taken into sub-batches whose data span,
+ * parity span (first start to last end, gaps included) and digests fit
+ * RSG_MIXED_STAGE_BYTES of staging; a larger stripe gets a sub-batch of its
+ * own.  Each sub-batch is one H2D copy of its data span, one small descriptor
+ * copy, one launch, and one D2H copy each of its parity span and digests: the
+ * bytes of the parity span between parity ranges are overwritten with
+ * unspecified values, so pack the arenas densely.  The host data span and
+ * parity span of a call must not intersect (RSG_ERR_INVALID_ARG). */
+#define RSG_MIXED_STAGE_BYTES (32u << 20)
+typedef struct rsg_stripe_desc {
+    uint64_t data_off, parity_off, shard_len;
+} rsg_stripe_desc;
+int rsg_encode_mixed_dev(rsg_ctx *ctx, int k, int m, size_t n, const rsg_stripe_desc *h_desc,
+                         const uint8_t *d_data, uint8_t *d_parity, uint8_t *d_digests, int algo,
+                         void *stream);
+int rsg_encode_mixed_host(rsg_ctx *ctx, int k, int m, size_t n, const rsg_stripe_desc *h_desc,
+                          const uint8_t *h_data, uint8_t *h_parity, uint8_t *h_digests, int algo);
+int rsg_encode_mixed_host_submit(rsg_ctx *ctx, int k, int m, size_t n, const rsg_stripe_desc *h_desc,
+                                 const uint8_t *h_data, uint8_t *h_parity, uint8_t *h_digests, int algo,
+                                 uint64_t *ticket);
+
 /* Page-lock / release host memory for DMA (hipHostRegister). */
 int rsg_pin(void *ptr, size_t bytes);
 int rsg_unpin(void *ptr);

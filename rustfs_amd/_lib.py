@@ -64,7 +64,14 @@ EXPORTED = (
     "rsg_encode_batch_host_submit", "rsg_poll", "rsg_wait", "rsg_set_kernel_timing", "rsg_last_kernel_ms",
     "rsg_set_record_engine", "rsg_decode_records_into_dev", "rsg_decode_records_submit",
     "rsg_heal_records_submit", "rsg_test_fail_subbatch", "rsg_set_tuning", "rsg_get_tuning",
+    "rsg_encode_mixed_dev", "rsg_encode_mixed_host", "rsg_encode_mixed_host_submit",
 )
+
+# Staging bytes per sub-batch of rsg_encode_mixed_host (include/rsgpu.h)
+RSG_MIXED_STAGE_BYTES = 32 << 20
+# rsg_stripe_desc (include/rsgpu.h): three little-endian u64 per stripe; a
+# numpy (n, 3) uint64 array [data_off, parity_off, shard_len] has its layout
+STRIPE_DESC_FIELDS = 3
 
 # Kernel-choice knobs (rsg_set_tuning, include/rsgpu.h) and their defaults:
 # set only through the ABI (the production library ignores RSG_* variables).
@@ -142,6 +149,9 @@ def load():
         L.rsg_test_fail_subbatch.argtypes = [P, I]
         L.rsg_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
         L.rsg_get_tuning.argtypes = [ctypes.c_char_p, ctypes.c_char_p, S]
+        L.rsg_encode_mixed_dev.argtypes = [P, I, I, S, P, P, P, P, I, P]
+        L.rsg_encode_mixed_host.argtypes = [P, I, I, S, P, P, P, P, I]
+        L.rsg_encode_mixed_host_submit.argtypes = [P, I, I, S, P, P, P, P, I, ctypes.POINTER(ctypes.c_uint64)]
         _lib = L
         return L
 

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +25,7 @@
 
 #include "../../include/rsgpu.h"
 #include "rs_kernels.h"
+#include "rs_mixed.h"
 
 namespace rsg {  // the kernel-choice knobs (rs_kernels.hip): 0 = ok, 1 = unknown name / bad value
 int set_tuning(const char* name, const char* value);
@@ -598,6 +600,46 @@ struct rsg_ctx {
         if (rec_free.size() < 16) rec_free.push_back(std::move(sc));  // else freed here
     }
 
+    // Descriptor tables of the mixed-length encode (rsg_encode_mixed_*): the
+    // device table a launch reads and the page-locked buffer it is filled
+    // through stay the library's until the launch has finished.  A call takes
+    // a table whose last use has completed (its event) or makes a new one,
+    // and puts it back with an event recorded behind its launch.
+    struct MixedTab {
+        RecScratch buf;  // d: the device table, h: its page-locked source
+        hipEvent_t used = nullptr;
+        ~MixedTab() {
+            if (used) {
+                (void)hipEventSynchronize(used);
+                (void)hipEventDestroy(used);
+            }
+        }
+    };
+    std::mutex mixed_mu;
+    std::vector<std::unique_ptr<MixedTab>> mixed_tabs;
+
+    std::unique_ptr<MixedTab> take_mixed_tab() {
+        std::lock_guard<std::mutex> g(mixed_mu);
+        for (size_t i = 0; i < mixed_tabs.size(); ++i) {
+            const hipError_t q = hipEventQuery(mixed_tabs[i]->used);
+            if (q == hipSuccess) {
+                std::unique_ptr<MixedTab> t = std::move(mixed_tabs[i]);
+                mixed_tabs.erase(mixed_tabs.begin() + (ptrdiff_t)i);
+                return t;
+            }
+            if (q == hipErrorNotReady && hipPeekAtLastError() == hipErrorNotReady) (void)hipGetLastError();
+        }
+        std::unique_ptr<MixedTab> t(new MixedTab());
+        if (hipEventCreateWithFlags(&t->used, hipEventDisableTiming) != hipSuccess) return nullptr;
+        return t;
+    }
+    // `t` was last used by work queued on `s`
+    void give_mixed_tab(std::unique_ptr<MixedTab> t, hipStream_t s) {
+        if (hipEventRecord(t->used, s) != hipSuccess) (void)hipStreamSynchronize(s);
+        std::lock_guard<std::mutex> g(mixed_mu);
+        mixed_tabs.push_back(std::move(t));
+    }
+
     HostLane lanes[kHostLanes];
     std::atomic<unsigned> next_lane{0};
 
@@ -804,6 +846,7 @@ void rsg_destroy(rsg_ctx* ctx) {
     }
     ctx->jobs.clear();  // events destroyed with the last reference
     ctx->rec_free.clear();
+    ctx->mixed_tabs.clear();  // each waits for its last launch
     delete ctx;
 }
 
@@ -2043,6 +2086,186 @@ int rsg_decode_records_into_dev(rsg_ctx* ctx, int k, int m, size_t shard_len, si
     int st = rsg_decode_records_submit(ctx, k, m, shard_len, n, d_files, algo, verify_surplus, nullptr, d_targets,
                                        target_stride, h_src, h_status, stream, &t);
     return st ? st : rsg_wait(ctx, t);
+}
+
+}  // extern "C"
+
+// ---- mixed-length batch (rs_mixed.hip, rs_mixed_plan.h) ----
+
+namespace {
+
+static_assert(sizeof(rsg_stripe_desc) == sizeof(rsg::mixed::StripeDesc) &&
+                  offsetof(rsg_stripe_desc, shard_len) == offsetof(rsg::mixed::StripeDesc, shard_len),
+              "rsg_stripe_desc is the planner's StripeDesc");
+
+const rsg::mixed::StripeDesc* plan_desc(const rsg_stripe_desc* d) {
+    return reinterpret_cast<const rsg::mixed::StripeDesc*>(d);
+}
+
+// Stripes [first, first + count) of a validated list on stream s: data at
+// d_data + data_off - data_lo, parity at d_parity + parity_off - parity_lo,
+// digests (d_dig null: none) at d_dig + (j - first)*(k+m)*32.
+int mixed_run(rsg_ctx* ctx, int k, int m, const rsg::mixed::StripeDesc* desc, size_t first, size_t count,
+              uint64_t data_lo, uint64_t parity_lo, const uint8_t* d_data, uint8_t* d_parity, uint8_t* d_dig, int algo,
+              hipStream_t s) {
+    if (count == 0) return RSG_OK;
+    const int T = k + m;
+    if (rsg::mixed::kernel_geometry(k, m)) {
+        // one launch: the planner's table through a page-locked buffer into
+        // device memory, both the library's until the launch has finished
+        auto cd = get_codec(k, m);
+        if (!cd) return RSG_ERR_INVALID_ARG;
+        std::vector<rsg::mixed::MixedDesc> tab;
+        rsg::mixed::order_for_kernel(desc, first, count, data_lo, parity_lo, tab);
+        const size_t bytes = tab.size() * sizeof(rsg::mixed::MixedDesc);
+        std::unique_ptr<rsg_ctx::MixedTab> mt = ctx->take_mixed_tab();
+        if (!mt) return RSG_ERR_DEVICE;
+        int st = mt->buf.ensure(bytes, bytes);
+        if (st) return st;  // never used: freed here
+        std::memcpy(mt->buf.h, tab.data(), bytes);
+        st = hip_status(hipMemcpyAsync(mt->buf.d, mt->buf.h, bytes, hipMemcpyHostToDevice, s));
+        if (!st) {
+            RowSet rs = encode_rows(*cd, 0);
+            rsg::GfApplyParams p;
+            fill_params(rs, 0, 0, d_data, d_parity, 0, 0, rsg::GF_MODE_STORE, nullptr, p);
+            rsg::HashParams h;
+            std::memset(&h, 0, sizeof(h));
+            if (d_dig) {
+                std::memcpy(h.key, hash_key(algo), sizeof(h.key));
+                h.out = d_dig;
+            }
+            st = hip_status(rsg::launch_encode_hash_mixed(p, h, (const rsg::mixed::MixedDesc*)mt->buf.d, count, s));
+        }
+        ctx->give_mixed_tab(std::move(mt), s);
+        return st;
+    }
+    // m == 0, m > 4 or k > 16: the per-length kernels, stripe by stripe
+    std::shared_ptr<Codec> cd;
+    if (m > 0 && !(cd = get_codec(k, m))) return RSG_ERR_INVALID_ARG;
+    for (size_t j = 0; j < count; ++j) {
+        const rsg::mixed::StripeDesc& e = desc[first + j];
+        const uint64_t len = e.shard_len;
+        const uint8_t* db = len ? d_data + (e.data_off - data_lo) : d_data;
+        uint8_t* pb = (len && m) ? d_parity + (e.parity_off - parity_lo) : d_parity;
+        if (m > 0 && len > 0) {
+            RowSet rs = encode_rows(*cd, len);
+            for (int r = 0; r < m; ++r) rs.out_off[r] = (uint64_t)r * len;  // parity shards from pb
+            int st = apply_rows(rs, db, pb, 0, 0, len, 1, rsg::GF_MODE_STORE, nullptr, s);
+            if (st) return st;
+        }
+        if (d_dig) {
+            uint8_t* out = d_dig + j * (size_t)T * 32;
+            int st = hash_messages(algo, db, len, (uint64_t)k, (uint64_t)k, len, 0, out, s);
+            if (!st && m > 0) st = hash_messages(algo, pb, len, (uint64_t)m, (uint64_t)m, len, 0, out + (size_t)k * 32, s);
+            if (st) return st;
+        }
+    }
+    return RSG_OK;
+}
+
+// Argument checks shared by the device and host forms; *want_hash: digests asked for.
+int mixed_check(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe_desc* h_desc, const uint8_t* data,
+                const uint8_t* parity, const uint8_t* digests, int algo, bool* want_hash) {
+    int st = enter(ctx);
+    if (st) return st;
+    if ((st = check_geometry(k, m))) return st;
+    if (algo != RSG_HASH_NONE && !hash_key(algo)) return RSG_ERR_INVALID_ARG;
+    *want_hash = digests && algo != RSG_HASH_NONE;
+    if (n == 0) return RSG_OK;
+    if (!h_desc || !data || (m > 0 && !parity) || n > 0x7fffffffull) return RSG_ERR_INVALID_ARG;
+    if (!rsg::mixed::validate(k, m, n, plan_desc(h_desc), (uint64_t)(uintptr_t)data, (uint64_t)(uintptr_t)parity))
+        return RSG_ERR_INVALID_ARG;
+    return RSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsg_encode_mixed_dev(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe_desc* h_desc, const uint8_t* d_data,
+                         uint8_t* d_parity, uint8_t* d_digests, int algo, void* stream) {
+    bool want_hash = false;
+    int st = mixed_check(ctx, k, m, n, h_desc, d_data, d_parity, d_digests, algo, &want_hash);
+    if (st || n == 0) return st;
+    return mixed_run(ctx, k, m, plan_desc(h_desc), 0, n, 0, 0, d_data, d_parity, want_hash ? d_digests : nullptr, algo,
+                     pick_stream(ctx, stream));
+}
+
+int rsg_encode_mixed_host_submit(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe_desc* h_desc,
+                                 const uint8_t* h_data, uint8_t* h_parity, uint8_t* h_digests, int algo,
+                                 uint64_t* ticket) {
+    if (!ticket) return RSG_ERR_INVALID_ARG;
+    *ticket = 0;
+    bool want_hash = false;
+    int st = mixed_check(ctx, k, m, n, h_desc, h_data, h_parity, h_digests, algo, &want_hash);
+    if (st) return st;
+    const rsg::mixed::StripeDesc* desc = plan_desc(h_desc);
+    std::vector<rsg::mixed::SubBatch> subs;
+    if (n) {
+        // the whole call's spans must not intersect: a sub-batch's parity span
+        // comes back whole, gaps included, and must not land on data
+        rsg::mixed::split(k, m, n, desc, want_hash, UINT64_MAX, n, subs);
+        const rsg::mixed::SubBatch& all = subs[0];
+        if (all.data_hi > all.data_lo && all.parity_hi > all.parity_lo &&
+            spans_overlap(h_data + all.data_lo, all.data_hi - all.data_lo, h_parity + all.parity_lo,
+                          all.parity_hi - all.parity_lo))
+            return RSG_ERR_INVALID_ARG;
+        rsg::mixed::split(k, m, n, desc, want_hash, RSG_MIXED_STAGE_BYTES, n, subs);
+    }
+    std::lock_guard<std::mutex> g(ctx->pipe_mu);
+    auto job = std::make_shared<rsg_ctx::Job>();
+    const bool work = n > 0 && (m > 0 || want_hash);
+    if (work) {
+        uint64_t need = RSG_MIXED_STAGE_BYTES;  // a stripe larger than that grows the stage
+        for (const auto& b : subs) need = std::max(need, rsg::mixed::stage_bytes(b, k, m, want_hash));
+        if ((st = ctx->ensure_pipeline((size_t)need))) return st;
+        bool used[rsg_ctx::kPipeSlots] = {};
+        const int fail_at = ctx->fail_subbatch.load();  // rsg_test_fail_subbatch (tests only)
+        int sub = 0;
+        for (const auto& b : subs) {
+            const int slot = (int)(ctx->next_slot++ % rsg_ctx::kPipeSlots);
+            used[slot] = true;
+            hipStream_t s = ctx->pipe_stream[slot];
+            const uint64_t dspan = b.data_hi - b.data_lo, pspan = b.parity_hi - b.parity_lo;
+            uint8_t* dd = ctx->d_stage[slot];
+            uint8_t* dp = dd + rsg::mixed::stage_round(dspan);
+            uint8_t* ddig = want_hash ? dp + rsg::mixed::stage_round(pspan) : nullptr;
+            if (dspan) st = hip_status(hipMemcpyAsync(dd, h_data + b.data_lo, dspan, hipMemcpyHostToDevice, s));
+            if (!st && sub == fail_at) st = RSG_ERR_DEVICE;  // fault injection (tests only)
+            if (!st) st = mixed_run(ctx, k, m, desc, b.first, b.count, b.data_lo, b.parity_lo, dd, dp, ddig, algo, s);
+            if (!st && pspan) st = hip_status(hipMemcpyAsync(h_parity + b.parity_lo, dp, pspan, hipMemcpyDeviceToHost, s));
+            if (!st && want_hash)
+                st = hip_status(hipMemcpyAsync(h_digests + b.first * (size_t)(k + m) * 32, ddig,
+                                               b.count * (size_t)(k + m) * 32, hipMemcpyDeviceToHost, s));
+            if (st) break;
+            ++sub;
+        }
+        for (int b = 0; b < rsg_ctx::kPipeSlots && !st; ++b) {
+            if (!used[b]) continue;
+            hipEvent_t e;
+            if ((st = hip_status(hipEventCreateWithFlags(&e, hipEventDisableTiming)))) break;
+            job->done.push_back(e);
+            st = hip_status(hipEventRecord(e, ctx->pipe_stream[b]));
+        }
+        if (st) {
+            // no ticket: drain every slot this job used before returning, so
+            // no copy outlives the call (rsg_encode_batch_host_submit's contract)
+            for (int b = 0; b < rsg_ctx::kPipeSlots; ++b)
+                if (used[b]) (void)hipStreamSynchronize(ctx->pipe_stream[b]);
+            return st;
+        }
+    }
+    *ticket = ctx->next_ticket++;
+    ctx->jobs.emplace(*ticket, std::move(job));
+    return RSG_OK;
+}
+
+int rsg_encode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe_desc* h_desc, const uint8_t* h_data,
+                          uint8_t* h_parity, uint8_t* h_digests, int algo) {
+    uint64_t t = 0;
+    int st = rsg_encode_mixed_host_submit(ctx, k, m, n, h_desc, h_data, h_parity, h_digests, algo, &t);
+    if (st) return st;
+    return rsg_wait(ctx, t);
 }
 
 int rsg_set_kernel_timing(rsg_ctx* ctx, int on) {

@@ -13,7 +13,9 @@ on the GPU and run asynchronously on the current torch stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import threading
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -196,6 +198,8 @@ class Erasure:
         self.block_size = block_size
         self.encoder = ReedSolomonEncoder(data_shards, parity_shards, device) if parity_shards > 0 else None
         self._device = device
+        self._mixed_arenas = None  # page-locked (data, parity, digests) of the mixed-length calls, reused
+        self._mixed_lock = threading.Lock()
 
     try_new = classmethod(lambda cls, k, m, b, device=None: cls(k, m, b, device))
 
@@ -263,6 +267,68 @@ class Erasure:
             for i in range(t):
                 dig[0, i] = np.frombuffer(HashAlgorithm.HighwayHash256S.hash_encode(buf[0, i], self._device), np.uint8)
         return [dig[0, i].tobytes() + buf[0, i].tobytes() for i in range(t)]
+
+    def encode_inline_shards_many(self, datas: Sequence) -> List[List[bytes]]:
+        """encode_inline_shards for many objects at once: entry j equals
+        ``encode_inline_shards(datas[j])`` (``[]`` for an empty object, which
+        submits no stripe).  The objects' zero-padded k*S_j data regions are
+        packed into one page-locked data arena, with a parity arena and a
+        digest array beside it (reused across calls), and parity and all
+        digests of every object come from one rsg_encode_mixed_host call."""
+        k, m, t = self.data_shards, self.parity_shards, self.total_shard_count()
+        arrs = [_as_array(d).reshape(-1).view(np.uint8) for d in datas]
+        live = [j for j, a in enumerate(arrs) if a.size]
+        out: List[List[bytes]] = [[] for _ in arrs]
+        if not live:
+            return out
+        S = np.array([calc_shard_size(arrs[j].size, k) for j in live], dtype=np.uint64)
+        desc = np.zeros((len(live), 3), dtype=np.uint64)
+        desc[:, 2] = S
+        desc[1:, 0] = np.cumsum(S[:-1] * np.uint64(k))
+        desc[1:, 1] = np.cumsum(S[:-1] * np.uint64(m))
+        nd, npar = int(S.sum()) * k, int(S.sum()) * m
+        with self.mixed_stage(nd, npar, len(live)) as (data, parity, dig):
+            for i, j in enumerate(live):
+                a, off, s = arrs[j], int(desc[i, 0]), int(S[i])
+                data[off:off + a.size] = a
+                data[off + a.size:off + k * s] = 0  # the pad up to k*S (erasure.rs:858-866)
+            self.encode_mixed_host(data, parity, desc, dig)
+            for i, j in enumerate(live):
+                do, po, s = int(desc[i, 0]), int(desc[i, 1]), int(S[i])
+                d = dig[i].tobytes()
+                out[j] = [d[32 * c:32 * c + 32] + data[do + c * s:do + (c + 1) * s].tobytes() for c in range(k)] + \
+                         [d[32 * (k + r):32 * (k + r) + 32] + parity[po + r * s:po + (r + 1) * s].tobytes()
+                          for r in range(m)]
+        return out
+
+    @contextlib.contextmanager
+    def mixed_stage(self, data_bytes: int, parity_bytes: int, n: int):
+        """Arenas for a mixed-length host call: (data, parity, digests (n, k+m,
+        32)) uint8 arrays of at least the sizes asked for, page-locked and
+        reused across calls (PutStage's role); a caller that finds them in use
+        by another thread gets pageable arrays of its own.  Contents are
+        unspecified on entry."""
+        t = self.total_shard_count()
+        if not self._mixed_lock.acquire(blocking=False):
+            yield (np.empty(data_bytes, np.uint8), np.empty(parity_bytes, np.uint8),
+                   np.empty((n, t, 32), np.uint8))
+            return
+        try:
+            have = self._mixed_arenas
+            if have is None or have[0].size < data_bytes or have[1].size < parity_bytes or have[2].size < n * t * 32:
+                import torch
+
+                def pinned(nbytes, old):  # grow by half again, so a slowly growing batch does not re-pin each call
+                    want = max(nbytes, 1)
+                    if old is not None and old.size >= want:
+                        return old
+                    return torch.empty(want + want // 2, dtype=torch.uint8).pin_memory().numpy()
+                old = have or (None, None, None)
+                have = self._mixed_arenas = (pinned(data_bytes, old[0]), pinned(parity_bytes, old[1]),
+                                             pinned(n * t * 32, old[2]))
+            yield have[0][:data_bytes], have[1][:parity_bytes], have[2][:n * t * 32].reshape(n, t, 32)
+        finally:
+            self._mixed_lock.release()
 
     # -- decode (erasure.rs:897-1019) --
     def decode_data(self, shards: List) -> None:
@@ -336,6 +402,74 @@ class Erasure:
             ctx.handle, self.data_shards, self.parity_shards, S, n, stripes.ctypes.data, S, t * S, d,
             algo if d else _lib.RSG_HASH_NONE, ctypes.byref(tk)), "Reed-Solomon encode failed")
         return HostBatchTicket(ctx, tk.value, (stripes, digests))
+
+    # -- mixed-length batches: every stripe its own shard length (rsg_encode_mixed_*) --
+    def _mixed_desc(self, desc, data_len: int, parity_len: int, digests_len: Optional[int]) -> np.ndarray:
+        """The (n, 3) uint64 descriptor array [data_off, parity_off, shard_len]
+        (rsg_stripe_desc), with every range checked against the arenas."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=np.uint64).reshape(-1, _lib.STRIPE_DESC_FIELDS))
+        k, m = self.data_shards, self.parity_shards
+        o = d[d[:, 2] != 0].astype(object)  # exact integers: an offset near 2^64 must not wrap
+        if o.shape[0] and ((o[:, 0] + k * o[:, 2]).max() > data_len or
+                           (m and (o[:, 1] + m * o[:, 2]).max() > parity_len)):
+            raise RsgError(_lib.RSG_ERR_INVALID_ARG, "mixed-length stripe outside its arena")
+        if digests_len is not None and digests_len < d.shape[0] * (k + m) * 32:
+            raise TypeError("digests must hold (n, k+m, 32) bytes")
+        return d
+
+    def encode_mixed(self, data, parity, desc, digests=None, algo: int = _lib.RSG_HASH_HIGHWAY256S,
+                     stream=None) -> None:
+        """Mixed-length batch on the device (rsg_encode_mixed_dev): `data` and
+        `parity` are contiguous cuda uint8 arenas (the same tensor for an
+        aliased layout such as a3), `desc` an (n, 3) array of [data_off,
+        parity_off, shard_len]; stripe j's k data shards lie back to back at
+        data_off, its m parity shards are written back to back at parity_off,
+        its k+m digests to digests[j] (cuda (n, k+m, 32), optional).
+        Asynchronous on the current torch stream; one launch for k <= 16,
+        m = 1..4."""
+        for a in (data, parity) + ((digests,) if digests is not None else ()):
+            if a.dtype.__str__() != "torch.uint8" or not a.is_cuda or not a.is_contiguous():
+                raise TypeError("arenas and digests must be contiguous cuda uint8 tensors")
+        d = self._mixed_desc(desc, data.numel(), parity.numel(), digests.numel() if digests is not None else None)
+        check(_lib.load().rsg_encode_mixed_dev(
+            _lib.context(_device_of(data)).handle, self.data_shards, self.parity_shards, d.shape[0], d.ctypes.data,
+            data.data_ptr(), parity.data_ptr(), digests.data_ptr() if digests is not None else None,
+            algo if digests is not None else _lib.RSG_HASH_NONE, _stream_of(data, stream)),
+            "Reed-Solomon encode failed")
+
+    def _mixed_host_args(self, data, parity, desc, digests):
+        for a in (data, parity) + ((digests,) if digests is not None else ()):
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or not a.flags.c_contiguous:
+                raise TypeError("arenas and digests must be C-contiguous uint8 arrays")
+        _writable(parity)
+        d = self._mixed_desc(desc, data.size, parity.size, digests.size if digests is not None else None)
+        return d, (digests.ctypes.data if digests is not None else None)
+
+    def encode_mixed_host(self, data: np.ndarray, parity: np.ndarray, desc, digests: Optional[np.ndarray] = None,
+                          algo: int = _lib.RSG_HASH_HIGHWAY256S) -> None:
+        """encode_mixed on host arenas (rsg_encode_mixed_host): sub-batches of
+        consecutive stripes pipelined H2D -> one launch -> D2H inside
+        librsgpu.  The parity arena's bytes between the parity ranges of a
+        sub-batch come back unspecified: pack the arenas densely."""
+        d, dg = self._mixed_host_args(data, parity, desc, digests)
+        check(_lib.load().rsg_encode_mixed_host(
+            _lib.context(self._device).handle, self.data_shards, self.parity_shards, d.shape[0], d.ctypes.data,
+            data.ctypes.data, parity.ctypes.data, dg, algo if dg else _lib.RSG_HASH_NONE),
+            "Reed-Solomon encode failed")
+
+    def encode_mixed_host_submit(self, data: np.ndarray, parity: np.ndarray, desc,
+                                 digests: Optional[np.ndarray] = None,
+                                 algo: int = _lib.RSG_HASH_HIGHWAY256S) -> "HostBatchTicket":
+        """Asynchronous encode_mixed_host (rsg_encode_mixed_host_submit): the
+        arrays must stay alive and untouched until the ticket is done."""
+        d, dg = self._mixed_host_args(data, parity, desc, digests)
+        tk = ctypes.c_uint64(0)
+        ctx = _lib.context(self._device)
+        check(_lib.load().rsg_encode_mixed_host_submit(
+            ctx.handle, self.data_shards, self.parity_shards, d.shape[0], d.ctypes.data, data.ctypes.data,
+            parity.ctypes.data, dg, algo if dg else _lib.RSG_HASH_NONE, ctypes.byref(tk)),
+            "Reed-Solomon encode failed")
+        return HostBatchTicket(ctx, tk.value, (data, parity, d, digests))
 
     def _host_batch_args(self, stripes, digests):
         if stripes.dtype != np.uint8 or stripes.ndim != 3 or not stripes.flags.c_contiguous:

@@ -12,6 +12,8 @@ what exercises the codec path:
   Full blocks go through one batched call (rsg_encode_batch_host) that returns
   parity and all bitrot digests in the same pass (the encode_batched dispatch
   point, encode.rs:795-919); the short tail block through encode_data.
+  put_objects takes many objects at once: all their blocks, short ones
+  included, are one mixed-length batch (rsg_encode_mixed_host).
 * GET: read every available shard file, verify each record before use
   (split_and_verify, bitrot.rs:227-247; a mismatching record marks that shard
   missing for the block), reconstruct missing data shards
@@ -50,7 +52,7 @@ import shutil
 import threading
 import time
 import uuid
-from typing import Iterator, List, Optional
+from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -137,6 +139,52 @@ class LocalErasureSet:
             if staged:
                 self._stage_lock.release()
         return self._commit(name, int(data.size), version)
+
+    def put_objects(self, items: Sequence[Tuple[str, object]]) -> List[dict]:
+        """PUT of many objects with one encode call: every block of every
+        object, full or short, is one stripe of one mixed-length batch
+        (rsg_encode_mixed_host: parity and all bitrot digests in one pass),
+        then each object is written and committed exactly as put_object does.
+        The shard files are byte-identical to put_object's.  Returns the
+        objects' metadata in order."""
+        e, k, m, t = self.erasure, self.k, self.m, self.k + self.m
+        bs = e.block_size
+        bodies = [np.frombuffer(bytes(d), dtype=np.uint8) if not isinstance(d, np.ndarray) else d.reshape(-1)
+                  for _, d in items]
+        # one stripe per block, in object order: (object, offset in its body, bytes, shard length)
+        blocks = [(j, b0, min(bs, body.size - b0), calc_shard_size(min(bs, body.size - b0), k))
+                  for j, body in enumerate(bodies) for b0 in range(0, body.size, bs)]
+        S = np.array([b[3] for b in blocks], dtype=np.uint64)
+        desc = np.zeros((len(blocks), 3), dtype=np.uint64)
+        desc[:, 2] = S
+        if len(blocks) > 1:
+            desc[1:, 0] = np.cumsum(S[:-1] * np.uint64(k))
+            desc[1:, 1] = np.cumsum(S[:-1] * np.uint64(m))
+        total = int(S.sum())
+        metas: List[dict] = []
+        with e.mixed_stage(total * k, total * m, len(blocks)) as (data, parity, dig):
+            for i, (j, b0, nbytes, s) in enumerate(blocks):
+                off = int(desc[i, 0])
+                data[off:off + nbytes] = bodies[j][b0:b0 + nbytes]
+                data[off + nbytes:off + k * s] = 0  # the pad up to k*S (erasure.rs:858-866)
+            if blocks:
+                e.encode_mixed_host(data, parity, desc, dig, algo=self.algo.value)
+            records: List[List[list]] = [[[] for _ in range(t)] for _ in bodies]
+            for i, (j, _, _, s) in enumerate(blocks):
+                do, po = int(desc[i, 0]), int(desc[i, 1])
+                for c in range(k):
+                    records[j][c] += [dig[i, c], data[do + c * s:do + (c + 1) * s]]
+                for r in range(m):
+                    records[j][k + r] += [dig[i, k + r], parity[po + r * s:po + (r + 1) * s]]
+            for j, (name, _) in enumerate(items):
+                version = uuid.uuid4().hex
+                try:
+                    self._write_records(name, records[j], None, version)
+                except BaseException:
+                    self._discard(name, version)
+                    raise
+                metas.append(self._commit(name, int(bodies[j].size), version))
+        return metas
 
     def _write_records(self, name: str, records: List[list], tail, version: str) -> None:
         e, t = self.erasure, self.k + self.m
