@@ -388,6 +388,69 @@ int rsg_encode_mixed_host_submit(rsg_ctx *ctx, int k, int m, size_t n, const rsg
                                  const uint8_t *h_data, uint8_t *h_parity, uint8_t *h_digests, int algo,
                                  uint64_t *ticket);
 
+/* ---- mixed-length batch GET: verify + rebuild n unrelated record stripes ----
+ * The read side of the above: per stripe, verify-before-use of each
+ * [hash][shard] record (bitrot.rs:139-247), then
+ * decode_data_with_reconstruction_verification (erasure.rs:935-973) with only
+ * the absent data shards filled (bridge.rs:274-307), over stripes whose shard
+ * lengths, sets of present shards and rot all differ.  The contract is
+ * rsg_decode_records_into_dev's, applied per stripe.
+ * files: k+m record arenas, one per disk; a NULL arena means shard i is absent
+ * for every stripe, whatever `present` says.  Stripe s (h_desc[s], a host array
+ * the call does not keep): shard i's record [32-byte digest][shard_len bytes]
+ * is at files[i] + rec_off when bit i of `present` is set; shard_len == 0: the
+ * records are bare digests of the empty message.
+ * Every record the decode of a stripe uses is hashed and compared with its
+ * header first; a mismatching record counts as absent for that stripe only.
+ * A data shard c whose record verifies is served from that record: bit c of
+ * h_served[s] is set and nothing is written for it.  Only the data shards no
+ * verified record serves are rebuilt, at out + out_off + c*shard_len, from
+ * the first k verified shards in ascending index.  With verify_surplus, a
+ * stripe that rebuilt data while holding more than k verified shards
+ * re-derives every surplus parity shard and compares it byte for byte.  When
+ * every data record of a stripe verifies, its parity records are not read.
+ * h_status[s]: RSG_OK, RSG_ERR_TOO_FEW_SHARDS (fewer than k verified) or
+ * RSG_ERR_INCONSISTENT_SOURCES; h_served[s] is unspecified for a failed stripe.
+ * algo: HIGHWAY256S or HIGHWAY256S_LEGACY.  Synchronous.
+ * The call leaves alone every byte of `out` outside the windows of rebuilt
+ * shards (the gaps and the windows of served shards included) and every byte
+ * of the sources.  The window of a data shard that `present` or a NULL arena
+ * declares absent is written before the stripe's verdict is known, so it holds
+ * unspecified bytes when the stripe fails.
+ * RSG_ERR_INVALID_ARG with nothing written: a `present` bit at or above k+m;
+ * record ranges [rec_off, +32+shard_len) or non-empty out ranges [out_off,
+ * +k*shard_len) not strictly ascending and disjoint in list order; a range
+ * that wraps the address space; the out span meeting the record span of an
+ * arena that is read; a NULL pointer; an unknown algo; k+m > 32
+ * (RSG_ERR_UNSUPPORTED).  Geometry errors as rsg_check_geometry; n == 0 is
+ * RSG_OK.
+ * k <= 16 with m <= 4 (m == 0 only verifies) run one launch per distinct set
+ * of readable shards, and again for the stripes in which a record failed its
+ * hash, under the reduced set (at most k+m rounds).  Other geometries give
+ * the same results through rsg_decode_records_into_dev, stripe by stripe;
+ * there a stripe with shard_len == 0 is judged by `present` alone.
+ *
+ * rsg_decode_mixed_dev: device arenas; runs on `stream` and waits for it.
+ *
+ * rsg_decode_mixed_host: host arenas, page-locked or pageable.  Consecutive
+ * stripes are taken into sub-batches that fit RSG_MIXED_STAGE_BYTES of the
+ * host-batch staging slots (a larger stripe gets a sub-batch of its own); a
+ * sub-batch copies up the record span (first record's start to last record's
+ * end) of every arena that some stripe of it may read, not only the files its
+ * plans read, and copies back only the out windows of shards it rebuilt. */
+typedef struct rsg_record_desc {
+    uint64_t rec_off;   /* shard i's record of this stripe at files[i] + rec_off */
+    uint64_t out_off;   /* a rebuilt data shard c is written to out + out_off + c*shard_len */
+    uint32_t shard_len; /* 0: the records are bare digests of the empty message */
+    uint32_t present;   /* bit i set: shard i's record of this stripe may be read (i < k+m) */
+} rsg_record_desc;
+int rsg_decode_mixed_dev(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_desc *h_desc,
+                         const uint8_t *const *d_files, int algo, int verify_surplus, uint8_t *d_out,
+                         uint32_t *h_served, int *h_status, void *stream);
+int rsg_decode_mixed_host(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_desc *h_desc,
+                          const uint8_t *const *h_files, int algo, int verify_surplus, uint8_t *h_out,
+                          uint32_t *h_served, int *h_status);
+
 /* Page-lock / release host memory for DMA (hipHostRegister). */
 int rsg_pin(void *ptr, size_t bytes);
 int rsg_unpin(void *ptr);

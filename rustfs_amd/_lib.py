@@ -65,6 +65,7 @@ EXPORTED = (
     "rsg_set_record_engine", "rsg_decode_records_into_dev", "rsg_decode_records_submit",
     "rsg_heal_records_submit", "rsg_test_fail_subbatch", "rsg_set_tuning", "rsg_get_tuning",
     "rsg_encode_mixed_dev", "rsg_encode_mixed_host", "rsg_encode_mixed_host_submit",
+    "rsg_decode_mixed_dev", "rsg_decode_mixed_host",
 )
 
 # Staging bytes per sub-batch of rsg_encode_mixed_host (include/rsgpu.h)
@@ -72,6 +73,9 @@ RSG_MIXED_STAGE_BYTES = 32 << 20
 # rsg_stripe_desc (include/rsgpu.h): three little-endian u64 per stripe; a
 # numpy (n, 3) uint64 array [data_off, parity_off, shard_len] has its layout
 STRIPE_DESC_FIELDS = 3
+# rsg_record_desc (include/rsgpu.h): the mixed-length GET's descriptor, 24
+# bytes per stripe; RECORD_DESC_DTYPE is its numpy structured dtype
+RECORD_DESC_FIELDS = (("rec_off", "<u8"), ("out_off", "<u8"), ("shard_len", "<u4"), ("present", "<u4"))
 
 # Kernel-choice knobs (rsg_set_tuning, include/rsgpu.h) and their defaults:
 # set only through the ABI (the production library ignores RSG_* variables).
@@ -152,6 +156,8 @@ def load():
         L.rsg_encode_mixed_dev.argtypes = [P, I, I, S, P, P, P, P, I, P]
         L.rsg_encode_mixed_host.argtypes = [P, I, I, S, P, P, P, P, I]
         L.rsg_encode_mixed_host_submit.argtypes = [P, I, I, S, P, P, P, P, I, ctypes.POINTER(ctypes.c_uint64)]
+        L.rsg_decode_mixed_dev.argtypes = [P, I, I, S, P, P, I, I, P, P, P, P]
+        L.rsg_decode_mixed_host.argtypes = [P, I, I, S, P, P, I, I, P, P, P]
         _lib = L
         return L
 

@@ -32,23 +32,12 @@
 
 namespace rsg {
 
-constexpr uint32_t kFusedChunk = mixed::kChunk;     // bytes per shard per step
-constexpr uint32_t kFusedPitch = kFusedChunk + 32;  // LDS row pitch: conflict-free ds_read_b64
-
 using mixed::MixedDesc;
 
 // chunk count of descriptor idx of the table (0 past its end)
 __device__ __forceinline__ uint32_t desc_chunks(const MixedDesc* desc, uint64_t idx, uint64_t n) {
     const uint32_t len = idx < n ? desc[idx].len : 0u;
     return (len >> 9) + ((len & (kFusedChunk - 1)) ? 1u : 0u);
-}
-
-// Wave-uniform copies (scalar registers).  __builtin_amdgcn_readfirstlane
-// returns int: widened as it is, a value with bit 31 set would sign-extend
-// into the upper half (an offset or length of 2 GiB or more).
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    return (uint64_t)uniform32((uint32_t)v) | ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32);
 }
 
 // Waves per SIMD asked of the register allocator: the packed kernel's rule up

@@ -2268,6 +2268,288 @@ int rsg_encode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe
     return rsg_wait(ctx, t);
 }
 
+}  // extern "C"
+
+// ---- mixed-length batch GET (rs_mixed_decode.hip, rs_mixed_decode_plan.h) ----
+
+namespace {
+
+static_assert(sizeof(rsg_record_desc) == sizeof(rsg::mixed::RecordDesc) &&
+                  offsetof(rsg_record_desc, shard_len) == offsetof(rsg::mixed::RecordDesc, shard_len) &&
+                  offsetof(rsg_record_desc, present) == offsetof(rsg::mixed::RecordDesc, present),
+              "rsg_record_desc is the planner's RecordDesc");
+
+// The kernel's arguments for one mask group: sources, lost rows, surplus rows
+// and their coefficient rows (plan_row over the codec's DecodePlan).
+int decode_mixed_params(Codec* cd, int k, int m, uint32_t mask, const rsg::mixed::MaskPlan& mp,
+                        const uint8_t* const* d_files, uint8_t* d_out, const uint64_t* key, uint8_t* d_flags,
+                        uint32_t* d_mismatch, rsg::DecodeMixedParams& p, int* row_shard) {
+    std::memset(&p, 0, sizeof(p));
+    const int e = (int)mp.lost.size(), R = e + (int)mp.surplus.size();
+    if (R > rsg::mixed::kDecMaxR) return RSG_ERR_UNSUPPORTED;
+    p.C = (uint32_t)k;
+    p.R = (uint32_t)R;
+    p.e = (uint32_t)e;
+    p.fstride = (uint32_t)(k + m);
+    p.out = d_out;
+    p.flags = d_flags;
+    p.mismatch = d_mismatch;
+    std::memcpy(p.key, key, sizeof(p.key));
+    for (int c = 0; c < k; ++c) {
+        p.file[c] = d_files[mp.src[c]];
+        row_shard[c] = mp.src[c];
+    }
+    for (int r = 0; r < R; ++r) row_shard[k + r] = -1;
+    if (R == 0) return RSG_OK;
+    std::vector<uint8_t> present((size_t)(k + m), 0);
+    for (int i = 0; i < k + m; ++i) present[i] = (mask >> i & 1u) ? 1 : 0;
+    std::shared_ptr<DecodePlan> plan = cd->plan(present.data());
+    if (!plan) return RSG_ERR_TOO_FEW_SHARDS;
+    std::vector<uint8_t> row((size_t)k);
+    for (int r = 0; r < R; ++r) {
+        const int shard = r < e ? mp.lost[r] : mp.surplus[r - e];
+        if (r < e) {
+            p.lost[r] = (uint32_t)shard;
+        } else {
+            p.file[k + r] = d_files[shard];
+            row_shard[k + r] = shard;
+        }
+        plan_row(*cd, *plan, shard, row.data());
+        for (int c = 0; c < k; ++c) coef_tables(row[c], p.tab[r][c]);
+    }
+    return RSG_OK;
+}
+
+// Stripes d[0 .. count) of a validated list on stream s, to the end (the
+// stream is waited for): shard i's record of stripe j at d_files[i] +
+// d[j].rec_off - rec_lo (d_files[i] null: absent), its out window at d_out +
+// d[j].out_off - out_lo.  masks_out[j] (optional): the verified shards the
+// stripe ended with.
+int decode_mixed_run(rsg_ctx* ctx, int k, int m, const rsg::mixed::RecordDesc* d, size_t count, uint64_t rec_lo,
+                     uint64_t out_lo, const uint8_t* const* d_files, int algo, bool verify_surplus, uint8_t* d_out,
+                     uint32_t* h_served, int* h_status, uint32_t* masks_out, hipStream_t s) {
+    namespace mx = rsg::mixed;
+    if (count == 0) return RSG_OK;
+    const int T = k + m;
+    const uint32_t data_bits = k >= 32 ? 0xffffffffu : (1u << k) - 1u;
+    uint64_t bases[32] = {};
+    for (int i = 0; i < T; ++i) bases[i] = (uint64_t)(uintptr_t)d_files[i];
+    const uint32_t arenas = mx::arena_mask(T, bases);
+    std::vector<uint32_t> masks(count);
+    for (size_t j = 0; j < count; ++j) masks[j] = d[j].present & arenas;
+    int st = RSG_OK;
+    std::vector<uint8_t> mismatch(count, 0);
+
+    if (mx::decode_kernel_geometry(k, m)) {
+        std::shared_ptr<Codec> cd;
+        if (m > 0 && !(cd = get_codec(k, m))) return RSG_ERR_INVALID_ARG;
+        const uint64_t* key = hash_key(algo);
+        const size_t fbytes = (size_t)mx::stage_round((uint64_t)count * T);
+        const size_t mbytes = (size_t)mx::stage_round((uint64_t)count * 4);
+        const size_t tbytes = count * sizeof(mx::DecDesc);
+        std::unique_ptr<rsg_ctx::MixedTab> mt = ctx->take_mixed_tab();
+        if (!mt) return RSG_ERR_DEVICE;
+        if ((st = mt->buf.ensure(fbytes + mbytes + tbytes, fbytes + mbytes + tbytes))) return st;
+        uint8_t* d_flags = mt->buf.d;
+        uint32_t* d_mis = (uint32_t*)(mt->buf.d + fbytes);
+        uint8_t* d_tab = mt->buf.d + fbytes + mbytes;
+        const uint8_t* h_flags = mt->buf.h;
+        const uint32_t* h_mis = (const uint32_t*)(mt->buf.h + fbytes);
+        uint8_t* h_tab = mt->buf.h + fbytes + mbytes;
+        st = hip_status(hipMemsetAsync(d_mis, 0, mbytes, s));
+
+        std::vector<uint32_t> todo(count), redo;
+        for (size_t j = 0; j < count; ++j) todo[j] = (uint32_t)j;
+        std::vector<mx::MaskGroup> groups;
+        std::vector<mx::DecDesc> tab;
+        std::vector<uint8_t> flags((size_t)count * T, 1);  // by shard
+        mx::MaskPlan mp;
+        struct Launch {
+            rsg::DecodeMixedParams p;
+            size_t at, n;
+            int row_shard[mx::kDecMaxC + mx::kDecMaxR];
+        };
+        std::vector<Launch> launches;
+        while (!st && !todo.empty()) {
+            mx::group_by_mask(masks.data(), todo, groups);
+            launches.clear();
+            size_t at = 0;
+            for (const mx::MaskGroup& g : groups) {
+                if (!mx::plan_mask(k, m, g.mask, verify_surplus, mp)) continue;  // TOO_FEW: no launch
+                launches.emplace_back();
+                Launch& l = launches.back();
+                if ((st = decode_mixed_params(cd.get(), k, m, g.mask, mp, d_files, d_out, key, d_flags, d_mis, l.p,
+                                              l.row_shard)))
+                    break;
+                mx::order_group_for_kernel(d, g.stripes, 0, rec_lo, out_lo, tab);
+                std::memcpy(h_tab + at * sizeof(mx::DecDesc), tab.data(), tab.size() * sizeof(mx::DecDesc));
+                l.at = at;
+                l.n = tab.size();
+                at += tab.size();
+            }
+            if (st || launches.empty()) break;
+            st = hip_status(hipMemcpyAsync(d_tab, h_tab, at * sizeof(mx::DecDesc), hipMemcpyHostToDevice, s));
+            for (size_t i = 0; i < launches.size() && !st; ++i)
+                st = hip_status(rsg::launch_decode_mixed(
+                    launches[i].p, (const mx::DecDesc*)(d_tab + launches[i].at * sizeof(mx::DecDesc)), launches[i].n, s));
+            if (!st) st = hip_status(hipMemcpyAsync(mt->buf.h, mt->buf.d, fbytes + mbytes, hipMemcpyDeviceToHost, s));
+            if (!st) st = hip_status(hipStreamSynchronize(s));
+            if (st) break;
+            // the kernel's flags are by row: to shard indices, for the planner
+            size_t li = 0;
+            for (const mx::MaskGroup& g : groups) {
+                if (mx::popcount32(g.mask) < k) continue;
+                const Launch& l = launches[li++];
+                for (uint32_t j : g.stripes)
+                    for (int row = 0; row < (int)(l.p.C + l.p.R); ++row)
+                        if (l.row_shard[row] >= 0)
+                            flags[(size_t)j * T + l.row_shard[row]] = h_flags[(size_t)j * T + row];
+            }
+            mx::redo_from_flags(k, m, verify_surplus, groups, 0, flags.data(), (size_t)T, masks.data(), redo);
+            todo.swap(redo);
+        }
+        if (!st)
+            for (size_t j = 0; j < count; ++j) mismatch[j] = h_mis[j] != 0;
+        if (st) (void)hipStreamSynchronize(s);
+        ctx->give_mixed_tab(std::move(mt), s);
+        if (st) return st;
+    } else {
+        // m > 4 or k > 16: the per-length engine, stripe by stripe
+        std::vector<const uint8_t*> fp((size_t)T);
+        std::vector<uint8_t*> tg((size_t)k);
+        std::vector<uint8_t> src((size_t)k);
+        for (size_t j = 0; j < count; ++j) {
+            const uint64_t len = d[j].shard_len;
+            if (len == 0 || mx::popcount32(masks[j]) < k) continue;  // judged by the mask below
+            for (int i = 0; i < T; ++i) fp[i] = (masks[j] >> i & 1u) ? d_files[i] + (d[j].rec_off - rec_lo) : nullptr;
+            for (int c = 0; c < k; ++c) tg[c] = d_out + (d[j].out_off - out_lo) + (uint64_t)c * len;
+            int one = RSG_OK;
+            if ((st = rsg_decode_records_into_dev(ctx, k, m, (size_t)len, 1, fp.data(), algo, verify_surplus ? 1 : 0,
+                                                  tg.data(), (size_t)((uint64_t)k * len), src.data(), &one, s)))
+                return st;
+            if (one == RSG_ERR_INCONSISTENT_SOURCES) mismatch[j] = 1;
+            else if (one != RSG_OK) masks[j] = 0;
+            else
+                for (int c = 0; c < k; ++c)
+                    if (!src[c]) masks[j] &= ~(1u << c);
+        }
+    }
+    for (size_t j = 0; j < count; ++j) {
+        h_status[j] = mx::popcount32(masks[j]) < k ? RSG_ERR_TOO_FEW_SHARDS
+                      : mismatch[j]                ? RSG_ERR_INCONSISTENT_SOURCES
+                                                   : RSG_OK;
+        h_served[j] = masks[j] & data_bits;
+        if (masks_out) masks_out[j] = masks[j];
+    }
+    return RSG_OK;
+}
+
+// Argument checks shared by the device and host forms.
+int decode_mixed_check(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_desc* h_desc,
+                       const uint8_t* const* files, int algo, const uint8_t* out, const uint32_t* h_served,
+                       const int* h_status) {
+    int st = enter(ctx);
+    if (st) return st;
+    if ((st = check_geometry(k, m))) return st;
+    if (!hash_key(algo)) return RSG_ERR_INVALID_ARG;
+    if (n == 0) return RSG_OK;
+    if (k + m > 32) return RSG_ERR_UNSUPPORTED;
+    if (!h_desc || !files || !out || !h_served || !h_status || n > 0x7fffffffull) return RSG_ERR_INVALID_ARG;
+    uint64_t bases[32] = {};
+    for (int i = 0; i < k + m; ++i) bases[i] = (uint64_t)(uintptr_t)files[i];
+    if (!rsg::mixed::validate_decode(k, m, n, reinterpret_cast<const rsg::mixed::RecordDesc*>(h_desc), bases,
+                                     (uint64_t)(uintptr_t)out))
+        return RSG_ERR_INVALID_ARG;
+    return RSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsg_decode_mixed_dev(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_desc* h_desc,
+                         const uint8_t* const* d_files, int algo, int verify_surplus, uint8_t* d_out,
+                         uint32_t* h_served, int* h_status, void* stream) {
+    int st = decode_mixed_check(ctx, k, m, n, h_desc, d_files, algo, d_out, h_served, h_status);
+    if (st || n == 0) return st;
+    return decode_mixed_run(ctx, k, m, reinterpret_cast<const rsg::mixed::RecordDesc*>(h_desc), n, 0, 0, d_files, algo,
+                            verify_surplus != 0, d_out, h_served, h_status, nullptr, pick_stream(ctx, stream));
+}
+
+int rsg_decode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_desc* h_desc,
+                          const uint8_t* const* h_files, int algo, int verify_surplus, uint8_t* h_out,
+                          uint32_t* h_served, int* h_status) {
+    namespace mx = rsg::mixed;
+    int st = decode_mixed_check(ctx, k, m, n, h_desc, h_files, algo, h_out, h_served, h_status);
+    if (st || n == 0) return st;
+    const mx::RecordDesc* desc = reinterpret_cast<const mx::RecordDesc*>(h_desc);
+    const int T = k + m;
+    const uint32_t data_bits = k >= 32 ? 0xffffffffu : (1u << k) - 1u;
+    std::vector<mx::DecSubBatch> subs;
+    mx::split_decode(k, T, n, desc, RSG_MIXED_STAGE_BYTES, n, subs);
+    uint64_t need = RSG_MIXED_STAGE_BYTES;  // a stripe larger than that grows the stage
+    for (const auto& b : subs) need = std::max(need, mx::decode_stage_bytes(b, T));
+    // The kernel's geometries stage through the host-batch slots (pipe_mu held
+    // to the end: the call is synchronous).  The per-length engine keeps its
+    // own tickets under pipe_mu, so the other geometries stage through a
+    // buffer of the call's own on the null stream.
+    const bool slots = mx::decode_kernel_geometry(k, m);
+    std::unique_lock<std::mutex> g(ctx->pipe_mu, std::defer_lock);
+    struct Own {
+        uint8_t* d = nullptr;
+        ~Own() {
+            if (d) (void)hipFree(d);
+        }
+    } own;
+    if (slots) {
+        g.lock();
+        if ((st = ctx->ensure_pipeline((size_t)need))) return st;
+    } else if ((st = hip_status(hipMalloc((void**)&own.d, (size_t)need)))) {
+        return st;
+    }
+    std::vector<uint32_t> masks;
+    for (const auto& b : subs) {
+        // one slot at a time: a sub-batch's verdicts decide what comes back
+        const int slot = slots ? (int)(ctx->next_slot++ % rsg_ctx::kPipeSlots) : 0;
+        hipStream_t s = slots ? ctx->pipe_stream[slot] : nullptr;
+        uint8_t* stage = slots ? ctx->d_stage[slot] : own.d;
+        const uint64_t rspan = b.rec_hi - b.rec_lo, ospan = b.out_hi - b.out_lo;
+        uint32_t may = 0;  // arenas some stripe of the sub-batch may read
+        for (size_t j = 0; j < b.count; ++j) may |= desc[b.first + j].present;
+        const uint8_t* dfiles[32] = {};
+        uint8_t* at = stage;
+        for (int i = 0; i < T && !st; ++i) {
+            if (!h_files[i] || !(may >> i & 1u)) continue;
+            dfiles[i] = at;
+            st = hip_status(hipMemcpyAsync(at, h_files[i] + b.rec_lo, rspan, hipMemcpyHostToDevice, s));
+            at += mx::stage_round(rspan);
+        }
+        uint8_t* dout = stage + (uint64_t)T * mx::stage_round(rspan);
+        masks.assign(b.count, 0);
+        if (!st)
+            st = decode_mixed_run(ctx, k, m, desc + b.first, b.count, b.rec_lo, b.out_lo, dfiles, algo,
+                                  verify_surplus != 0, dout, h_served + b.first, h_status + b.first, masks.data(), s);
+        // back: the windows of the shards a good stripe rebuilt, nothing else
+        for (size_t j = 0; j < b.count && !st; ++j) {
+            const mx::RecordDesc& e = desc[b.first + j];
+            if (h_status[b.first + j] != RSG_OK || e.shard_len == 0 || ospan == 0) continue;
+            for (int c = 0; c < k && !st; ++c) {
+                if (masks[j] & data_bits & (1u << c)) continue;
+                int c1 = c + 1;  // a run of rebuilt shards is one copy
+                while (c1 < k && !(masks[j] & (1u << c1))) ++c1;
+                const uint64_t off = e.out_off + (uint64_t)c * e.shard_len;
+                st = hip_status(hipMemcpyAsync(h_out + off, dout + (off - b.out_lo), (uint64_t)(c1 - c) * e.shard_len,
+                                               hipMemcpyDeviceToHost, s));
+                c = c1 - 1;
+            }
+        }
+        const int sy = hip_status(hipStreamSynchronize(s));
+        if (!st) st = sy;
+        if (st) return st;
+    }
+    return RSG_OK;
+}
+
 int rsg_set_kernel_timing(rsg_ctx* ctx, int on) {
     int st = enter(ctx);
     if (st) return st;

@@ -471,6 +471,131 @@ class Erasure:
             "Reed-Solomon encode failed")
         return HostBatchTicket(ctx, tk.value, (data, parity, d, digests))
 
+    # -- mixed-length GET: every stripe its own shard length and present set (rsg_decode_mixed_*) --
+    def _record_desc(self, desc, file_lens: Sequence[Optional[int]], out_len: int) -> np.ndarray:
+        """The rsg_record_desc array of `desc` (a structured array of
+        _lib.RECORD_DESC_FIELDS, or (n, 4) integers [rec_off, out_off,
+        shard_len, present]), with every stripe checked against its arenas
+        before anything reaches the library."""
+        dt = np.dtype(list(_lib.RECORD_DESC_FIELDS))
+        if isinstance(desc, np.ndarray) and desc.dtype == dt:
+            d = np.ascontiguousarray(desc.reshape(-1))
+        else:
+            rows = [tuple(int(v) for v in r) for r in np.asarray(desc, dtype=object).reshape(-1, 4)]
+            if any(not (0 <= r[0] < 1 << 64 and 0 <= r[1] < 1 << 64 and 0 <= r[2] < 1 << 32 and 0 <= r[3] < 1 << 32)
+                   for r in rows):
+                raise RsgError(_lib.RSG_ERR_INVALID_ARG, "mixed-length record descriptor out of range")
+            d = np.array(rows, dtype=dt) if rows else np.zeros(0, dtype=dt)
+        k, t = self.data_shards, self.total_shard_count()
+        if len(file_lens) != t:
+            raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT, f"invalid shard count: got {len(file_lens)}")
+        if d.size:
+            rec_end = d["rec_off"].astype(object) + 32 + d["shard_len"].astype(object)  # exact integers: no wrap
+            out_end = d["out_off"].astype(object) + k * d["shard_len"].astype(object)
+            live = d["shard_len"] != 0
+            if live.any() and out_end[live].max() > out_len:
+                raise RsgError(_lib.RSG_ERR_INVALID_ARG, "mixed-length stripe outside its out arena")
+            for i, n in enumerate(file_lens):
+                if n is None:
+                    continue
+                use = (d["present"] >> np.uint32(i) & np.uint32(1)).astype(bool) if i < 32 else np.zeros(d.size, bool)
+                if use.any() and rec_end[use].max() > n:
+                    raise RsgError(_lib.RSG_ERR_INVALID_ARG, f"mixed-length record outside arena {i}")
+        return d
+
+    def decode_mixed(self, files: Sequence, desc, out, verify_surplus: bool = True,
+                     algo: int = _lib.RSG_HASH_HIGHWAY256S, stream=None):
+        """Mixed-length batch GET on the device (rsg_decode_mixed_dev):
+        `files[i]` is shard i's record arena (a contiguous cuda uint8 tensor,
+        or None: absent for every stripe), `desc` lists per stripe [rec_off,
+        out_off, shard_len, present]; every record a stripe's decode uses is
+        verified against its 32-byte header first, and only the data shards no
+        verified record serves are rebuilt, at out + out_off + c*shard_len.
+        Returns (status, served): per stripe an rsg_status and the bit mask of
+        data shards served from their records.  Synchronous."""
+        t = self.total_shard_count()
+        for a in [f for f in files if f is not None] + [out]:
+            if a.dtype.__str__() != "torch.uint8" or not a.is_cuda or not a.is_contiguous():
+                raise TypeError("arenas and out must be contiguous cuda uint8 tensors")
+        d = self._record_desc(desc, [f.numel() if f is not None else None for f in files], out.numel())
+        n = d.size
+        status, served = (ctypes.c_int * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+        fp = (ctypes.c_void_p * t)(*[f.data_ptr() if f is not None else None for f in files])
+        check(_lib.load().rsg_decode_mixed_dev(
+            _lib.context(_device_of(out)).handle, self.data_shards, self.parity_shards, n, d.ctypes.data, fp, algo,
+            1 if verify_surplus else 0, out.data_ptr(), served, status, _stream_of(out, stream)),
+            "mixed-length decode failed")
+        return _lib.status_list(status, n), list(served[:n])
+
+    def decode_mixed_host(self, files: Sequence, desc, out: np.ndarray, verify_surplus: bool = True,
+                          algo: int = _lib.RSG_HASH_HIGHWAY256S):
+        """decode_mixed on host arenas (rsg_decode_mixed_host): numpy uint8
+        arrays, page-locked or pageable; sub-batches of consecutive stripes go
+        through the host-batch staging slots, and only the windows of rebuilt
+        shards of good stripes come back into `out`."""
+        t = self.total_shard_count()
+        for a in [f for f in files if f is not None] + [out]:
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or not a.flags.c_contiguous:
+                raise TypeError("arenas and out must be C-contiguous uint8 arrays")
+        _writable(out)
+        d = self._record_desc(desc, [f.size if f is not None else None for f in files], out.size)
+        n = d.size
+        status, served = (ctypes.c_int * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+        fp = (ctypes.c_void_p * t)(*[f.ctypes.data if f is not None else None for f in files])
+        check(_lib.load().rsg_decode_mixed_host(
+            _lib.context(self._device).handle, self.data_shards, self.parity_shards, n, d.ctypes.data, fp, algo,
+            1 if verify_surplus else 0, out.ctypes.data, served, status), "mixed-length decode failed")
+        return _lib.status_list(status, n), list(served[:n])
+
+    def decode_inline_shards_many(self, objects: Sequence, sizes: Sequence[int],
+                                  algo: int = _lib.RSG_HASH_HIGHWAY256S) -> list:
+        """The inverse of encode_inline_shards_many: objects[j] is a list of
+        k+m ``[hash][shard]`` byte strings (None, or a string of the wrong
+        length: the shard is not there) of an object of sizes[j] bytes.  Entry
+        j of the result is the object's bytes, or the RsgError instance (not
+        raised) that verify-before-use followed by a per-object
+        decode_data_with_reconstruction_verification would have raised, so one
+        bad object does not lose the rest.  A size of 0 gives b"" and submits
+        no stripe.  Every object is one stripe of one rsg_decode_mixed_host
+        call."""
+        k, t = self.data_shards, self.total_shard_count()
+        out: list = [b""] * len(objects)
+        live = [j for j, sz in enumerate(sizes) if sz]
+        if not live:
+            return out
+        S = [calc_shard_size(int(sizes[j]), k) for j in live]
+        dt = np.dtype(list(_lib.RECORD_DESC_FIELDS))
+        desc = np.zeros(len(live), dtype=dt)
+        desc["shard_len"] = S
+        recs = np.array([32 + s for s in S], dtype=np.uint64)
+        desc["rec_off"][1:] = np.cumsum(recs[:-1])
+        desc["out_off"][1:] = np.cumsum(np.array(S[:-1], dtype=np.uint64) * np.uint64(k))
+        arenas = [np.zeros(int(recs.sum()), dtype=np.uint8) for _ in range(t)]
+        for i, j in enumerate(live):
+            shards = objects[j]
+            if len(shards) != t:
+                raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT, f"object {j}: invalid shard count: got {len(shards)}")
+            off, want, present = int(desc["rec_off"][i]), 32 + S[i], 0
+            for c, r in enumerate(shards):
+                if r is not None and len(r) == want:
+                    arenas[c][off:off + want] = np.frombuffer(r, dtype=np.uint8)
+                    present |= 1 << c
+            desc["present"][i] = present
+        rebuilt = np.zeros(int(sum(S)) * k, dtype=np.uint8)
+        status, served = self.decode_mixed_host(arenas, desc, rebuilt, True, algo)
+        for i, j in enumerate(live):
+            if status[i] == _lib.RSG_ERR_TOO_FEW_SHARDS:
+                out[j] = RsgError(status[i], "read quorum lost")
+            elif status[i] == _lib.RSG_ERR_INCONSISTENT_SOURCES:
+                out[j] = InvalidDataError(status[i])
+            elif status[i] != _lib.RSG_OK:
+                out[j] = RsgError(status[i], "mixed-length decode failed")
+            else:
+                ro, oo, s = int(desc["rec_off"][i]) + 32, int(desc["out_off"][i]), S[i]
+                out[j] = b"".join((arenas[c][ro:ro + s] if served[i] >> c & 1 else rebuilt[oo + c * s:oo + (c + 1) * s])
+                                  .tobytes() for c in range(k))[:int(sizes[j])]
+        return out
+
     def _host_batch_args(self, stripes, digests):
         if stripes.dtype != np.uint8 or stripes.ndim != 3 or not stripes.flags.c_contiguous:
             raise TypeError("stripes must be a C-contiguous uint8 array (n, k+m, S)")

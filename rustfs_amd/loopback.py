@@ -375,6 +375,93 @@ class LocalErasureSet:
     def get_object(self, name: str) -> bytes:
         return self.get_object_range(name)
 
+    def get_objects(self, names: Sequence[str], return_exceptions: bool = False) -> list:
+        """GET of many objects with one decode call, the read side of
+        put_objects: every block of every object, full or short, is one stripe
+        of one mixed-length batch (rsg_decode_mixed_host: verify-before-use of
+        each record, then only the data shards no verified record serves are
+        rebuilt).  Each shard file is read whole into its disk's host arena,
+        all disks at equal offsets; a missing file, a file of the wrong length
+        or a disk not holding the chosen metadata version is absent for that
+        object's stripes, as _open_shards decides.  Each result equals
+        get_object(name).  A failing object's exception stands in its place
+        with return_exceptions; otherwise the first one is raised."""
+        e, k, t = self.erasure, self.k, self.k + self.m
+        bs, S = e.block_size, e.shard_size()
+        results: list = [None] * len(names)
+        raws: List[Optional[List[Optional[bytes]]]] = [None] * len(names)
+        sizes = [0] * len(names)
+        for j, name in enumerate(names):
+            try:
+                meta = self._meta(name)
+                sizes[j] = int(meta["size"])
+                if sizes[j] == 0:
+                    results[j] = b""
+                    continue
+                fds = self._open_shards(name, sizes[j], meta["version"], meta["disks"])
+                raw: List[Optional[bytes]] = []
+                try:
+                    for fd in fds:
+                        raw.append(None if fd is None else os.pread(fd, os.fstat(fd).st_size, 0))
+                finally:
+                    for fd in fds:
+                        if fd is not None:
+                            os.close(fd)
+                raws[j] = raw
+            except Exception as ex:  # no metadata, no read quorum on it, an unreadable disk
+                results[j] = ex
+        # one stripe per block, in object order: (object, bytes, shard length, record offset, out offset)
+        blocks = []
+        file_off = {}
+        rec_at = out_at = 0
+        for j, raw in enumerate(raws):
+            if raw is None:
+                continue
+            file_off[j] = rec_at
+            for b0 in range(0, sizes[j], bs):
+                nbytes = min(bs, sizes[j] - b0)
+                s = calc_shard_size(nbytes, k)
+                blocks.append((j, nbytes, s, rec_at, out_at))
+                rec_at += 32 + s
+                out_at += k * s
+        if blocks:
+            desc = np.zeros(len(blocks), dtype=np.dtype(list(_lib.RECORD_DESC_FIELDS)))
+            desc["shard_len"] = [b[2] for b in blocks]
+            desc["rec_off"] = [b[3] for b in blocks]
+            desc["out_off"] = [b[4] for b in blocks]
+            arenas = [np.empty(rec_at, dtype=np.uint8) for _ in range(t)]
+            present = {}
+            for j, off in file_off.items():
+                mask = 0
+                for i, r in enumerate(raws[j]):
+                    if r is not None:
+                        arenas[i][off:off + len(r)] = np.frombuffer(r, dtype=np.uint8)
+                        mask |= 1 << i
+                present[j] = mask
+            desc["present"] = [present[b[0]] for b in blocks]
+            rebuilt = np.empty(max(out_at, 1), dtype=np.uint8)
+            status, served = e.decode_mixed_host(arenas, desc, rebuilt, True, self.algo.value)
+            parts: dict = {j: [] for j in file_off}
+            for i, (j, nbytes, s, ro, oo) in enumerate(blocks):
+                if isinstance(parts[j], Exception):
+                    continue
+                if status[i] == _lib.RSG_ERR_TOO_FEW_SHARDS:
+                    parts[j] = _lib.RsgError(status[i], "read quorum lost")
+                elif status[i] != _lib.RSG_OK:
+                    parts[j] = _lib.InvalidDataError(status[i]) if status[i] == _lib.RSG_ERR_INCONSISTENT_SOURCES \
+                        else _lib.RsgError(status[i], f"get {names[j]}")
+                else:
+                    blk = b"".join((arenas[c][ro + 32:ro + 32 + s] if served[i] >> c & 1
+                                    else rebuilt[oo + c * s:oo + (c + 1) * s]).tobytes() for c in range(k))
+                    parts[j].append(blk[:nbytes])
+            for j, p in parts.items():
+                results[j] = p if isinstance(p, Exception) else b"".join(p)
+        if not return_exceptions:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
+
     # ----------------------------------------------------------------- HEAL
     def heal_object(self, name: str, targets: List[int]) -> None:
         """Rewrite the part files of the disks in `targets` from the others."""

@@ -1,0 +1,294 @@
+// Stand-alone check of the mixed-length GET's host planner
+// (rustfs_amd/csrc/rs_mixed_decode_plan.h), built by the host compiler with
+// AddressSanitizer + UBSan and run directly (tests/test_mixed_decode_plan.py).
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <set>
+#include <vector>
+
+#include "../../rustfs_amd/csrc/rs_mixed_decode_plan.h"
+
+using namespace rsg::mixed;
+
+#define CHECK(c)                                                      \
+    do {                                                              \
+        if (!(c)) {                                                   \
+            fprintf(stderr, "%s:%d: CHECK(%s)\n", __FILE__, __LINE__, #c); \
+            exit(1);                                                  \
+        }                                                             \
+    } while (0)
+
+namespace {
+
+// A valid list: records at odd offsets with 1..3 byte gaps, out windows packed
+// with the same gaps.
+std::vector<RecordDesc> make(int k, const std::vector<uint32_t>& lens, const std::vector<uint32_t>& present) {
+    std::vector<RecordDesc> d(lens.size());
+    uint64_t r = 1, o = 3;
+    for (size_t i = 0; i < lens.size(); ++i) {
+        d[i] = RecordDesc{r, o, lens[i], present[i % present.size()]};
+        r += kRecHeader + lens[i] + 1 + i % 3;
+        o += (uint64_t)k * lens[i] + 1 + i % 3;
+    }
+    return d;
+}
+
+void test_validation() {
+    const int k = 4, m = 2, t = k + m;
+    const uint64_t A = 0x100000000ull;  // arenas far apart
+    uint64_t files[6], out = 0x900000000ull;
+    for (int i = 0; i < t; ++i) files[i] = A * (uint64_t)(i + 1);
+    const std::vector<uint32_t> lens = {0, 1, 7, 8, 513, 0, 87382};
+    std::vector<RecordDesc> d = make(k, lens, {0x3f});
+    CHECK(validate_decode(k, m, d.size(), d.data(), files, out));
+    CHECK(validate_decode(k, m, 0, nullptr, files, out));
+    CHECK(validate_decode(k, 0, d.size(), make(k, lens, {0xf}).data(), files, out));  // m = 0
+    // zero-length stripes: out offsets are not looked at
+    {
+        auto e = d;
+        e[0].out_off = UINT64_MAX;
+        e[5].out_off = 0;
+        CHECK(validate_decode(k, m, e.size(), e.data(), files, out));
+    }
+    // a present bit at or above k+m
+    {
+        auto e = d;
+        e[2].present = 1u << t;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e[2].present = 0x80000000u;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+    }
+    // record ranges not ascending / overlapping (a bare digest still occupies 32 bytes)
+    {
+        auto e = d;
+        e[1].rec_off = e[0].rec_off + kRecHeader - 1;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e = d;
+        std::swap(e[3].rec_off, e[4].rec_off);
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e = d;
+        e[6].rec_off = e[5].rec_off;  // equal starts
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+    }
+    // out ranges not ascending / overlapping
+    {
+        auto e = d;
+        e[3].out_off = e[2].out_off + (uint64_t)k * e[2].shard_len - 1;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e = d;
+        std::swap(e[2].out_off, e[4].out_off);
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+    }
+    // ranges that wrap the address space
+    {
+        auto e = d;
+        e[6].rec_off = UINT64_MAX - 40;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e = d;
+        e[6].rec_off = UINT64_MAX - files[t - 1] - 100;  // wraps only relative to the highest arena
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e = d;
+        e[6].out_off = UINT64_MAX - 8;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+        e = d;
+        e[6].out_off = UINT64_MAX - out - 8;
+        CHECK(!validate_decode(k, m, e.size(), e.data(), files, out));
+    }
+    // the out span meets a source arena's record span: only one that is used
+    {
+        uint64_t f2[6];
+        for (int i = 0; i < t; ++i) f2[i] = files[i];
+        f2[5] = out + 100;
+        CHECK(!validate_decode(k, m, d.size(), d.data(), f2, out));
+        auto e = make(k, lens, {0x1f});  // shard 5 never read
+        CHECK(validate_decode(k, m, e.size(), e.data(), f2, out));
+        f2[5] = 0;  // a NULL arena, whatever `present` says
+        CHECK(validate_decode(k, m, d.size(), d.data(), f2, out));
+        // all stripes empty: no out span
+        auto z = make(k, {0, 0, 0}, {0x3f});
+        f2[5] = out;
+        CHECK(validate_decode(k, m, z.size(), z.data(), f2, out));
+    }
+    CHECK(!validate_decode(0, 2, d.size(), d.data(), files, out));
+    CHECK(!validate_decode(30, 3, 0, nullptr, files, out));  // k + m > 32
+    CHECK(!validate_decode(k, m, d.size(), nullptr, files, out));
+}
+
+void test_plans() {
+    MaskPlan p;
+    // RS(4,2), all present: nothing rebuilt, no parity read
+    CHECK(plan_mask(4, 2, 0x3f, true, p));
+    CHECK(p.src == std::vector<int>({0, 1, 2, 3}) && p.lost.empty() && p.surplus.empty());
+    CHECK(p.read_mask() == 0xfu);
+    // data shard 1 absent: sources 0 2 3 4, surplus 5 (only with verify_surplus)
+    CHECK(plan_mask(4, 2, 0x3d, true, p));
+    CHECK(p.src == std::vector<int>({0, 2, 3, 4}) && p.lost == std::vector<int>({1}) &&
+          p.surplus == std::vector<int>({5}));
+    CHECK(p.read_mask() == 0x3du);
+    CHECK(plan_mask(4, 2, 0x3d, false, p));
+    CHECK(p.surplus.empty() && p.read_mask() == 0x1du);
+    // exactly k, then k - 1
+    CHECK(plan_mask(4, 2, 0x35, true, p));
+    CHECK(p.src == std::vector<int>({0, 2, 4, 5}) && p.lost == std::vector<int>({1, 3}) && p.surplus.empty());
+    CHECK(!plan_mask(4, 2, 0x31, true, p));
+    CHECK(!plan_mask(4, 2, 0, true, p));
+    CHECK(plan_mask(5, 0, 0x1f, true, p));  // m = 0 only verifies
+    CHECK(p.lost.empty() && p.surplus.empty());
+    CHECK(!plan_mask(5, 0, 0x1e, true, p));
+    // the computed rows never exceed m
+    for (uint32_t mask = 0; mask < (1u << 12); ++mask)
+        if (plan_mask(8, 4, mask, true, p)) CHECK(p.lost.size() + p.surplus.size() <= 4 && p.src.size() == 8);
+    CHECK(decode_kernel_geometry(16, 4) && decode_kernel_geometry(5, 0) && !decode_kernel_geometry(10, 6) &&
+          !decode_kernel_geometry(17, 3));
+}
+
+// groups of 1, SPW and SPW+1 stripes out of three interleaved masks
+void test_grouping_and_order() {
+    const int k = 8, m = 4, spw = decode_spw_for(k + 4);
+    const uint32_t A = 0xfff, B = 0xffd, C = 0x3f;  // C: fewer than k bits
+    std::vector<uint32_t> masks;
+    for (int i = 0; i < spw + 1; ++i) {
+        masks.push_back(B);
+        if (i < spw) masks.push_back(C);
+        if (i == 1) masks.push_back(A);
+    }
+    const size_t n = masks.size();
+    std::vector<uint32_t> lens(n);
+    for (size_t i = 0; i < n; ++i) lens[i] = (uint32_t)((i * 700) % 2000);  // caller order != kernel order
+    std::vector<RecordDesc> d = make(k, lens, {0xfff});
+    std::vector<uint32_t> todo(n);
+    for (size_t i = 0; i < n; ++i) todo[i] = (uint32_t)i;
+    std::vector<MaskGroup> g;
+    group_by_mask(masks.data(), todo, g);
+    CHECK(g.size() == 3 && g[0].mask == B && g[1].mask == C && g[2].mask == A);
+    CHECK(g[0].stripes.size() == (size_t)spw + 1 && g[1].stripes.size() == (size_t)spw && g[2].stripes.size() == 1);
+    std::set<uint32_t> seen;
+    for (const MaskGroup& gr : g) {
+        for (size_t i = 0; i < gr.stripes.size(); ++i) {
+            CHECK(masks[gr.stripes[i]] == gr.mask);
+            CHECK(i == 0 || gr.stripes[i - 1] < gr.stripes[i]);  // stable: caller order inside a group
+            CHECK(seen.insert(gr.stripes[i]).second);
+        }
+        MaskPlan p;
+        CHECK(plan_mask(k, m, gr.mask, true, p) == (gr.mask != C));  // fewer than k bits: no launch
+        std::vector<DecDesc> tab;
+        order_group_for_kernel(d.data(), gr.stripes, 0, d[0].rec_off, 3, tab);
+        CHECK(tab.size() == gr.stripes.size());
+        std::set<uint32_t> jobs;
+        for (size_t i = 0; i < tab.size(); ++i) {
+            CHECK(i == 0 || chunks_of(tab[i - 1].len) >= chunks_of(tab[i].len));
+            CHECK(jobs.insert(tab[i].job).second);
+            const RecordDesc& s = d[tab[i].job];  // job maps back to the caller's index
+            CHECK(masks[tab[i].job] == gr.mask && tab[i].len == s.shard_len);
+            CHECK(tab[i].rec_off == s.rec_off - d[0].rec_off);
+            CHECK(tab[i].out_off == (s.shard_len ? s.out_off - 3 : 0));
+        }
+        CHECK(jobs == std::set<uint32_t>(gr.stripes.begin(), gr.stripes.end()));
+    }
+    CHECK(seen.size() == n);
+    // a sub-batch's jobs are relative to its first stripe
+    std::vector<uint32_t> part = {5, 6, 7};
+    std::vector<DecDesc> tab;
+    order_group_for_kernel(d.data(), part, 5, d[5].rec_off, 0, tab);
+    for (const DecDesc& x : tab) CHECK(x.job < 3 && x.len == d[5 + x.job].shard_len);
+    // an empty todo list
+    group_by_mask(masks.data(), {}, g);
+    CHECK(g.empty());
+}
+
+void test_split() {
+    const int k = 4, t = 6;
+    std::vector<uint32_t> lens;
+    for (int i = 0; i < 40; ++i) lens.push_back(i % 7 == 0 ? 0u : 1000u * (uint32_t)(i % 5 + 1));
+    lens[20] = 300000;  // larger than the stage: a sub-batch of its own
+    std::vector<RecordDesc> d = make(k, lens, {0x3f});
+    const uint64_t stage = 200000;
+    std::vector<DecSubBatch> subs;
+    split_decode(k, t, d.size(), d.data(), stage, d.size(), subs);
+    size_t next = 0;
+    bool alone = false;
+    for (const DecSubBatch& b : subs) {
+        CHECK(b.first == next && b.count >= 1);
+        next += b.count;
+        CHECK(b.count == 1 || decode_stage_bytes(b, t) <= stage);
+        if (b.first == 20) alone = b.count == 1;
+        CHECK(b.rec_lo == d[b.first].rec_off);
+        const RecordDesc& last = d[b.first + b.count - 1];
+        CHECK(b.rec_hi == last.rec_off + kRecHeader + last.shard_len);
+        for (size_t j = 0; j < b.count; ++j) {
+            const RecordDesc& s = d[b.first + j];
+            if (s.shard_len) CHECK(b.out_lo <= s.out_off && s.out_off + (uint64_t)k * s.shard_len <= b.out_hi);
+        }
+    }
+    CHECK(next == d.size() && alone && subs.size() >= 3);
+    split_decode(k, t, d.size(), d.data(), UINT64_MAX, d.size(), subs);
+    CHECK(subs.size() == 1 && subs[0].count == d.size());
+    split_decode(k, t, d.size(), d.data(), UINT64_MAX, 7, subs);  // max_count
+    CHECK(subs.size() == 6 && subs.back().count == 5);
+    split_decode(k, t, 0, d.data(), stage, 1, subs);
+    CHECK(subs.empty());
+    auto z = make(k, {0, 0, 0}, {0x3f});  // only empty stripes: no out span
+    split_decode(k, t, z.size(), z.data(), stage, z.size(), subs);
+    CHECK(subs.size() == 1 && subs[0].out_lo == 0 && subs[0].out_hi == 0 && subs[0].rec_hi > subs[0].rec_lo);
+}
+
+// Rounds of launch -> flags -> regrouping, driven by a table of records that
+// are rotten; ends in at most k+m rounds with the verified sets.
+void test_redo() {
+    const int k = 4, m = 2, t = k + m;
+    const size_t n = 9;
+    // rotten[s]: bits of stripe s's records that fail their hash when read
+    const uint32_t rotten[n] = {0, 0x02, 0x10, 0x20, 0x3f, 0x0f, 0x01, 0x12, 0};
+    uint32_t masks[n] = {0x3f, 0x3f, 0x3d, 0x3d, 0x3f, 0x3f, 0x07, 0x3f, 0x3e};
+    const uint32_t start[n] = {0x3f, 0x3f, 0x3d, 0x3d, 0x3f, 0x3f, 0x07, 0x3f, 0x3e};
+    std::vector<uint32_t> todo(n), redo;
+    for (size_t i = 0; i < n; ++i) todo[i] = (uint32_t)i;
+    std::vector<uint8_t> flags(n * t, 1);
+    std::vector<MaskGroup> groups;
+    int rounds = 0;
+    while (!todo.empty()) {
+        CHECK(++rounds <= t + 1);  // the last round finds nothing to redo
+        group_by_mask(masks, todo, groups);
+        MaskPlan p;
+        for (const MaskGroup& g : groups) {
+            if (!plan_mask(k, m, g.mask, true, p)) continue;
+            for (uint32_t s : g.stripes)  // what the kernel would write: one flag per row read
+                for (int i = 0; i < t; ++i)
+                    if (p.read_mask() >> i & 1u) flags[s * t + (size_t)i] = (rotten[s] >> i & 1u) ? 0 : 1;
+        }
+        std::vector<uint32_t> before(masks, masks + n);
+        redo_from_flags(k, m, true, groups, 0, flags.data(), (size_t)t, masks, redo);
+        for (size_t i = 0; i < redo.size(); ++i) {
+            CHECK(i == 0 || redo[i - 1] < redo[i]);
+            CHECK(popcount32(masks[redo[i]]) < popcount32(before[redo[i]]));  // at least one bit fewer
+        }
+        for (size_t s = 0; s < n; ++s) CHECK((masks[s] & ~before[s]) == 0);
+        todo = redo;
+    }
+    CHECK(rounds <= t);
+    for (size_t s = 0; s < n; ++s) {
+        // no record that was read and failed stays; nothing healthy is dropped
+        CHECK(masks[s] == (start[s] & ~rotten[s]) || popcount32(masks[s]) < k ||
+              (masks[s] & ~rotten[s]) == masks[s]);
+        MaskPlan p;
+        if (plan_mask(k, m, masks[s], true, p)) CHECK((p.read_mask() & rotten[s]) == 0);
+    }
+    CHECK(masks[0] == 0x3f && masks[8] == 0x3e);
+    CHECK(masks[1] == 0x3d);                  // rotten data shard found with all data assumed present
+    CHECK(masks[2] == 0x2d && masks[3] == 0x1d);  // a rotten source parity, a rotten surplus parity
+    CHECK(popcount32(masks[4]) < k && popcount32(masks[5]) < k && popcount32(masks[6]) < k);
+    CHECK(masks[7] == 0x2d);  // parity 4 is found rotten only after data 1 is
+}
+
+}  // namespace
+
+int main() {
+    test_validation();
+    test_plans();
+    test_grouping_and_order();
+    test_split();
+    test_redo();
+    printf("mixed decode plan ok\n");
+    return 0;
+}
