@@ -2,6 +2,8 @@
 // librsgpu (rs_kernels.hip, rs_decode.hip): GF(2^8) table multiply (v_perm)
 // and 16-byte access helpers, lane-parallel HighwayHash-256 (HHQuad), the
 // raw LDS barrier and the LDS-DMA ring constants of the one-pass kernels.
+// What only the three fused kernels share (step geometry, table fill, GF
+// rows, hasher walk, instantiation dispatch) builds on these in rs_fused.h.
 // Internal; included once per translation unit.
 #pragma once
 

@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include "rs_device.h"
+#include "rs_fused.h"
 #include "gf_bitslice.h"
 
 namespace rsg {
@@ -372,17 +373,9 @@ __global__ __launch_bounds__(256) void k_hh256_quad(const HashParams p) {
 // Barriers are raw s_barrier with an explicit lgkmcnt wait: __syncthreads()
 // would also drain the in-flight global loads (vmcnt(0)).  Stripes past the end
 // of the batch keep their waves in the barrier sequence with memory ops masked.
-constexpr uint32_t kFusedChunk = 512;                 // bytes per shard per step
-constexpr uint32_t kFusedPitch = kFusedChunk + 32;    // LDS row pitch: conflict-free ds_read_b64
-
-constexpr int fused_spw_for(int T) {  // stripes per workgroup: fill hasher waves, cap LDS
-    return (T % 16 == 0) ? 1 : (T % 8 == 0) ? 2 : (T % 4 == 0 || T <= 6) ? 4 : 2;
-}
-template <int T>
-constexpr int fused_spw() {
-    return fused_spw_for(T);
-}
-
+// The step geometry, the table fill and the GF rows are the fused kernels'
+// shared parts (rs_fused.h).
+//
 // ABLATE_ (measurement builds only: tools/kbench/fused_variants.hip defines
 // RSG_MEASUREMENT_BUILD before including this file): bit 0 skips the GF
 // arithmetic, bit 1 the hash updates, bit 3 records each wave's HW_ID in its
@@ -396,9 +389,7 @@ void k_encode_hash_fused(const GfApplyParams p,
                                                                                               const HashParams h) {
     static_assert(ABLATE_ == 0 || RSG_MEASUREMENT_BUILD, "ablation variants exist in measurement builds only");
     constexpr int ABLATE = RSG_MEASUREMENT_BUILD ? ABLATE_ : 0;
-    // LDS: [C][R] coefficient tables (32 B each: T0 T0' T1 T1' | T2), then
-    // SPW x (C+R) chunk rows.  Tables are read from LDS (broadcast) at their
-    // use: held in registers across the chunk loop they cost 64+ VGPRs.
+    // LDS: [C][R] coefficient tables (32 B each), then SPW x (C+R) chunk rows
     extern __shared__ uint8_t lds_all[];
     constexpr int T = C + R;
     constexpr uint32_t kTabBytes = C * R * 32;
@@ -408,12 +399,7 @@ void k_encode_hash_fused(const GfApplyParams p,
     const uint64_t n = h.n;
     const uint32_t chunks = p.units;  // ceil(S / kFusedChunk)
 
-    for (uint32_t i = threadIdx.x; i < (uint32_t)(C * R); i += blockDim.x) {
-        const int c = i / R, r = i % R;
-        uint8_t* d = lds_all + i * 32;
-        *(uint4*)d = make_uint4(p.tab[r][c][0], p.tab[r][c][1], p.tab[r][c][2], p.tab[r][c][3]);
-        *(uint32_t*)(d + 16) = p.tab[r][c][4];
-    }
+    fused_tables_to_lds<C, R>(p.tab, lds_all);
     __syncthreads();
     if constexpr (ABLATE & 8) {
         const uint64_t stripe = (uint64_t)blockIdx.x * SPW + (wave < SPW ? wave : 0);
@@ -441,41 +427,16 @@ void k_encode_hash_fused(const GfApplyParams p,
         const uint32_t m7 = vgpr_const(0x07070707u), m3 = vgpr_const(0x03030303u);
         // the GF rows of one chunk (x: 8 bytes of every data shard per lane)
         auto rows_of = [&](const uint2 (&x)[C], uint32_t (&acc)[R][2]) {
-            // opaque per-iteration zero: keeps the table reads at their use
-            // instead of hoisted out of the loop into (spilled) registers
-            uint32_t tz;
-            asm volatile("s_mov_b32 %0, 0" : "=s"(tz));
-            const uint8_t* tabs = lds_all + tz;
-            uint32_t pend[R][2];
+            if constexpr (ABLATE & 1) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = pend[r][0] = pend[r][1] = 0u;
+                for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = 0u;
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                if constexpr (ABLATE & 1) {
+                for (int c = 0; c < C; ++c) {
                     acc[c % R][0] ^= x[c].x;
                     acc[c % R][1] ^= x[c].y;
-                    continue;
                 }
-                const uint32_t s0a = x[c].x & m7, s0b = x[c].y & m7;
-                const uint32_t s1a = (x[c].x >> 3) & m7, s1b = (x[c].y >> 3) & m7;
-                const uint32_t s2a = (x[c].x >> 6) & m3, s2b = (x[c].y >> 6) & m3;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const uint8_t* tp = tabs + (c * R + r) * 32;  // wave-uniform: broadcast read
-                    const uint4 t4 = *(const uint4*)tp;
-                    const uint32_t t2 = *(const uint32_t*)(tp + 16);
-                    gf_fold(c & 1, acc[r][0], pend[r][0], __builtin_amdgcn_perm(t4.y, t4.x, s0a),
-                            __builtin_amdgcn_perm(t4.w, t4.z, s1a), __builtin_amdgcn_perm(t2, t2, s2a));
-                    gf_fold(c & 1, acc[r][1], pend[r][1], __builtin_amdgcn_perm(t4.y, t4.x, s0b),
-                            __builtin_amdgcn_perm(t4.w, t4.z, s1b), __builtin_amdgcn_perm(t2, t2, s2b));
-                }
-            }
-            if constexpr (C % 2 == 1 && !(ABLATE & 1)) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    acc[r][0] ^= pend[r][0];
-                    acc[r][1] ^= pend[r][1];
-                }
+            } else {
+                fused_gf_rows<C, R>(lds_all, m7, m3, x, acc);
             }
         };
         // a chunk's data and parity rows into this stripe's LDS rows, between
@@ -542,6 +503,7 @@ void k_encode_hash_fused(const GfApplyParams p,
         const uint8_t* row = row0 + 8 * q;
         HHQuad st;
         hhq_init(st, h.key, q);
+        // not fused_hash_stream: one length peels the last chunk, and ABLATE & 2 sits in the update
 #pragma unroll 1
         for (uint32_t ch = 0; ch + 1 < chunks; ++ch) {
             lds_barrier();  // A
@@ -1534,7 +1496,7 @@ struct FusedPick {
 // workgroup (A/B only, measurement builds).
 template <int C, int R>
 static FusedPick fused_entry(bool packed) {
-    constexpr int spw = fused_spw<C + R>();
+    constexpr int spw = fused_spw_for(C + R);
     if constexpr (spw == 1) {
         (void)packed;
         return {k_encode_hash_fused<C, R, 1>, 1, 1 + (C + R + 15) / 16};
@@ -1547,37 +1509,11 @@ static FusedPick fused_entry(bool packed) {
     }
 }
 
-template <int C>
-static FusedPick pick_fused_r(int R, bool packed) {
-    switch (R) {
-        case 1: return fused_entry<C, 1>(packed);
-        case 2: return fused_entry<C, 2>(packed);
-        case 3: return fused_entry<C, 3>(packed);
-        case 4: return fused_entry<C, 4>(packed);
-    }
-    return {nullptr, 0, 0};
-}
-
 static FusedPick pick_fused(int C, int R, bool packed) {
-    switch (C) {
-        case 1: return pick_fused_r<1>(R, packed);
-        case 2: return pick_fused_r<2>(R, packed);
-        case 3: return pick_fused_r<3>(R, packed);
-        case 4: return pick_fused_r<4>(R, packed);
-        case 5: return pick_fused_r<5>(R, packed);
-        case 6: return pick_fused_r<6>(R, packed);
-        case 7: return pick_fused_r<7>(R, packed);
-        case 8: return pick_fused_r<8>(R, packed);
-        case 9: return pick_fused_r<9>(R, packed);
-        case 10: return pick_fused_r<10>(R, packed);
-        case 11: return pick_fused_r<11>(R, packed);
-        case 12: return pick_fused_r<12>(R, packed);
-        case 13: return pick_fused_r<13>(R, packed);
-        case 14: return pick_fused_r<14>(R, packed);
-        case 15: return pick_fused_r<15>(R, packed);
-        case 16: return pick_fused_r<16>(R, packed);
-    }
-    return {nullptr, 0, 0};
+    return dispatch_int<1, 16>(C, FusedPick{}, [=](auto c) {
+        return dispatch_int<1, 4>(
+            R, FusedPick{}, [=](auto r) { return fused_entry<decltype(c)::value, decltype(r)::value>(packed); });
+    });
 }
 
 // The packed table kernel takes shards of any length at any alignment (a
@@ -1818,29 +1754,12 @@ hipError_t launch_encode_hash_fused(GfApplyParams p, HashParams h, uint64_t shar
 
 using RingKernel = void (*)(const GfApplyParams, const HashParams, const uint32_t);
 
-template <int C>
-static RingKernel pick_ring_r(int R) {
-    switch (R) {
-        case 1: return k_encode_hash_ring<C, 1>;
-        case 2: return k_encode_hash_ring<C, 2>;
-        case 3: return k_encode_hash_ring<C, 3>;
-        case 4: return k_encode_hash_ring<C, 4>;
-    }
-    return nullptr;
-}
-
 static RingKernel pick_ring(int C, int R) {
-    switch (C) {
-        case 1: return pick_ring_r<1>(R);
-        case 2: return pick_ring_r<2>(R);
-        case 3: return pick_ring_r<3>(R);
-        case 4: return pick_ring_r<4>(R);
-        case 5: return pick_ring_r<5>(R);
-        case 6: return pick_ring_r<6>(R);
-        case 7: return pick_ring_r<7>(R);
-        case 8: return pick_ring_r<8>(R);
-    }
-    return nullptr;
+    return dispatch_int<1, 8>(C, RingKernel(nullptr), [R](auto c) {
+        return dispatch_int<1, 4>(R, RingKernel(nullptr), [](auto r) -> RingKernel {
+            return k_encode_hash_ring<decltype(c)::value, decltype(r)::value>;
+        });
+    });
 }
 
 size_t ring_lds_bytes(int C, int R, uint32_t E) {

@@ -9,9 +9,6 @@
 
 namespace rsg {
 
-constexpr uint32_t kFusedChunk = mixed::kChunk;     // bytes per shard per step
-constexpr uint32_t kFusedPitch = kFusedChunk + 32;  // LDS row pitch: conflict-free ds_read_b64
-
 #ifdef __HIPCC__
 // Wave-uniform copies (scalar registers).  __builtin_amdgcn_readfirstlane
 // returns int: widened as it is, a value with bit 31 set would sign-extend

@@ -3,13 +3,16 @@
 // shards no verified record serves (erasure.rs:935-973), over n unrelated
 // stripes in one launch, each with its own shard length.
 //
-// k_decode_mixed<C,R,SPW> keeps the structure of k_encode_hash_mixed
-// (rs_mixed.hip): SPW GF waves (one per stripe), ceil(SPW*T/16) hasher waves
-// (one 4-lane quad per row, T = C + R), coefficient tables, then the records'
-// 32-byte headers, then SPW x T rows of kFusedPitch in LDS, an A/B barrier
-// pair per 512-byte chunk, a per-stripe descriptor table in device memory
-// (mixed::DecDesc).  One launch serves one mask group, so every stripe of a
-// workgroup shares the decode plan (DecodeMixedParams, rs_mixed.h):
+// k_decode_mixed<C,R,SPW> is one of the three fused kernels built from the
+// parts in rs_fused.h (table fill, GF rows, hasher walk, step geometry; the
+// three-form tail loader stays per kernel), beside k_encode_hash_mixed (rs_mixed.hip): SPW GF waves (one per
+// stripe), ceil(SPW*T/16) hasher waves (one 4-lane quad per row, T = C + R),
+// coefficient tables, then the records' 32-byte headers, then SPW x T rows of
+// kFusedPitch in LDS, an A/B barrier pair per 512-byte chunk, a per-stripe
+// descriptor table in device memory (mixed::DecDesc).  Its hashers compare
+// each digest with the record's header instead of writing it out.  One launch
+// serves one mask group, so every stripe of a workgroup shares the decode
+// plan (DecodeMixedParams, rs_mixed.h):
 //   row c < C      source c: read from file[c], hashed, input of the GF rows
 //   row C + r, r < e   rebuilt data shard lost[r]: computed, stored to out
 //   row C + r, r >= e  surplus shard: read from file[C + r], hashed, and
@@ -19,11 +22,10 @@
 // out of LDS, so what is used is what was verified.  R = 0 only verifies.
 //
 // Barrier count: every wave of a workgroup runs one __syncthreads() and then
-// exactly 2*wg_chunks lds_barrier() calls, wg_chunks = the maximum chunk count
-// over the workgroup's SPW descriptors (len = 0 past the end of the table),
-// made wave-uniform with readfirstlane from the same descriptor words in
-// every wave.  No barrier sits under a condition on a stripe's own length, on
-// `live`, on the plan or on a lane.
+// exactly 2*wg_chunks lds_barrier() calls (the argument stands at
+// fused_hash_stream, rs_fused.h), wg_chunks = the maximum chunk count over the
+// workgroup's SPW descriptors (len = 0 past the end of the table); nor does a
+// barrier sit under a condition on the plan.
 //
 // Built in kMdecParts (4) translation units: part i (RSG_MDEC_PART=i)
 // instantiates C = i+1, i+1+PARTS, ...; without RSG_MDEC_PART: the launcher.
@@ -32,6 +34,7 @@
 #include <stdint.h>
 
 #include "rs_device.h"
+#include "rs_fused.h"
 #include "rs_mixed.h"
 
 namespace rsg {
@@ -55,12 +58,6 @@ RSG_MDEC_PART_DECL(3)
 #undef RSG_MDEC_PART_DECL
 
 #ifdef RSG_MDEC_PART
-
-// chunk count of descriptor idx of the table (0 past its end)
-__device__ __forceinline__ uint32_t dec_chunks(const DecDesc* desc, uint64_t idx, uint64_t n) {
-    const uint32_t len = idx < n ? desc[idx].len : 0u;
-    return (len >> 9) + ((len & (kFusedChunk - 1)) ? 1u : 0u);
-}
 
 // Waves per SIMD asked of the register allocator: per geometry, the highest
 // request at which the resource-usage report shows no scratch
@@ -103,20 +100,14 @@ void k_decode_mixed(const DecodeMixedParams p, const DecDesc* __restrict__ desc,
     // row `row` is read from its file (wave-uniform; `row` a constant after unrolling)
     auto is_read = [&](int row) { return row < C || (uint32_t)(row - C) >= e; };
 
-    if constexpr (R > 0) {
-        for (uint32_t i = threadIdx.x; i < (uint32_t)(C * R); i += blockDim.x) {
-            const int c = i / R, r = i % R;
-            uint8_t* d = lds_all + i * 32;
-            *(uint4*)d = make_uint4(p.tab[r][c][0], p.tab[r][c][1], p.tab[r][c][2], p.tab[r][c][3]);
-            *(uint32_t*)(d + 16) = p.tab[r][c][4];
-        }
-    }
+    fused_tables_to_lds<C, R>(p.tab, lds_all);
 
-    // The workgroup's step count: the same SPW descriptor words in every wave.
+    // The workgroup's step count: the same SPW descriptor words in every wave
+    // (no chunk past the end of the table).
     uint32_t wgc = 0;
 #pragma unroll
     for (int s = 0; s < SPW; ++s) {
-        const uint32_t c = dec_chunks(desc, first + s, n);
+        const uint32_t c = fused_chunks(first + s < n ? desc[first + s].len : 0u);
         wgc = c > wgc ? c : wgc;
     }
     const uint32_t wg_chunks = uniform32(wgc);
@@ -140,52 +131,10 @@ void k_decode_mixed(const DecodeMixedParams p, const DecDesc* __restrict__ desc,
 
     if (gf) {
         // ------------------------------ GF wave ------------------------------
-        const uint32_t my_chunks = (uint32_t)(S >> 9) + ((S & (kFusedChunk - 1)) ? 1u : 0u);
+        const uint32_t my_chunks = fused_chunks(S);
         uint8_t* ob = p.out + oo;
         uint8_t* my_rows = rows + wave * kStripeRows;
         const uint32_t m7 = vgpr_const(0x07070707u), m3 = vgpr_const(0x03030303u);
-        // the R computed rows of one chunk (x: 8 bytes of every source per lane)
-        auto rows_of = [&](const uint2 (&x)[T], uint32_t (&acc)[RR][2]) {
-            if constexpr (R > 0) {
-                // opaque per-iteration zero: keeps the table reads at their use
-                // instead of hoisted out of the loop into (spilled) registers
-                uint32_t tz;
-                asm volatile("s_mov_b32 %0, 0" : "=s"(tz));
-                const uint8_t* tabs = lds_all + tz;
-                uint32_t pend[RR][2];
-#pragma unroll
-                for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = pend[r][0] = pend[r][1] = 0u;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const uint32_t s0a = x[c].x & m7, s0b = x[c].y & m7;
-                    const uint32_t s1a = (x[c].x >> 3) & m7, s1b = (x[c].y >> 3) & m7;
-                    const uint32_t s2a = (x[c].x >> 6) & m3, s2b = (x[c].y >> 6) & m3;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const uint8_t* tp = tabs + (c * R + r) * 32;  // wave-uniform: broadcast read
-                        const uint4 t4 = *(const uint4*)tp;
-                        const uint32_t t2 = *(const uint32_t*)(tp + 16);
-                        gf_fold(c & 1, acc[r][0], pend[r][0], __builtin_amdgcn_perm(t4.y, t4.x, s0a),
-                                __builtin_amdgcn_perm(t4.w, t4.z, s1a), __builtin_amdgcn_perm(t2, t2, s2a));
-                        gf_fold(c & 1, acc[r][1], pend[r][1], __builtin_amdgcn_perm(t4.y, t4.x, s0b),
-                                __builtin_amdgcn_perm(t4.w, t4.z, s1b), __builtin_amdgcn_perm(t2, t2, s2b));
-                    }
-                }
-                if constexpr (C % 2 == 1) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        acc[r][0] ^= pend[r][0];
-                        acc[r][1] ^= pend[r][1];
-                    }
-                }
-                // The rows are complete here: without this the compiler sinks
-                // each row's lookups into the store / compare branch that uses
-                // it (`r < e` is a run-time test) and keeps all C x R tables
-                // in registers across the branches (RS(8,4): over 256 VGPRs).
-#pragma unroll
-                for (int r = 0; r < R; ++r) asm volatile("" : "+v"(acc[r][0]), "+v"(acc[r][1]));
-            }
-        };
         // Chunk ch of every row that is read, fetched one step ahead (in
         // flight across the barriers), the encode kernel's three forms: whole
         // 8-byte loads while the chunk ends at or before S; the shard's last 8
@@ -247,7 +196,14 @@ void k_decode_mixed(const DecodeMixedParams p, const DecDesc* __restrict__ desc,
                     const bool whole = cb + kFusedChunk <= S;
                     const uint32_t tail = whole ? kFusedChunk : (uint32_t)(S - cb);
                     uint32_t acc[RR][2];
-                    rows_of(x, acc);
+                    // the R computed rows of this chunk (x: 8 bytes of every source per lane)
+                    fused_gf_rows<C, R>(lds_all, m7, m3, x, acc);
+                    // The rows are complete here: without this the compiler sinks
+                    // each row's lookups into the store / compare branch that uses
+                    // it (`r < e` is a run-time test) and keeps all C x R tables
+                    // in registers across the branches (RS(8,4): over 256 VGPRs).
+#pragma unroll
+                    for (int r = 0; r < R; ++r) asm volatile("" : "+v"(acc[r][0]), "+v"(acc[r][1]));
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         if ((uint32_t)r < e) {  // a lost data row: nothing written at or past S
@@ -289,41 +245,21 @@ void k_decode_mixed(const DecodeMixedParams p, const DecDesc* __restrict__ desc,
         const bool live = g < (uint32_t)(SPW * T) && idx < n && (row < (uint32_t)C || row - (uint32_t)C >= e);
         const uint32_t len = live ? desc[idx].len : 0u;
         const uint32_t job = live ? desc[idx].job : 0u;
-        const uint32_t my_chunks = (len >> 9) + ((len & (kFusedChunk - 1)) ? 1u : 0u);  // per quad
-        const uint32_t tail = my_chunks ? len - (my_chunks - 1) * kFusedChunk : 0u;     // 1..512
+        const uint32_t my_chunks = fused_chunks(len);                                // per quad
+        const uint32_t tail = my_chunks ? len - (my_chunks - 1) * kFusedChunk : 0u;  // 1..512
         const uint8_t* row0 = rows + (live ? ls * kStripeRows + row * kFusedPitch : 0);
-        const uint8_t* rp = row0 + 8 * q;
         const uint8_t* hdr = hdrs + (live ? (ls * T + row) * 32 : 0);
         uint8_t* flag = p.flags + (uint64_t)job * p.fstride + row;
         HHQuad st;
         hhq_init(st, p.key, q);
         // digest against the record's header; the quad's verdict, written whole
-        auto finish = [&]() {
+        fused_hash_stream(st, row0, q, live, my_chunks, tail, wg_chunks, [&] {
             const uint64_t h = hhq_digest(st, q);
             uint32_t ok = h == *(const uint64_t*)(hdr + 8 * q) ? 1u : 0u;
             ok &= quad_swap_pairs(ok);
             ok &= quad_swap_halves(ok);
             if (q == 0) *flag = (uint8_t)ok;
-        };
-        if (live && my_chunks == 0) finish();  // the empty message
-#pragma unroll 1
-        for (uint32_t ch = 0; ch < wg_chunks; ++ch) {
-            lds_barrier();  // A
-            lds_barrier();  // B
-            if (live && ch + 1 < my_chunks) {
-#pragma unroll 4
-                for (int t = 0; t < (int)(kFusedChunk / 32); ++t)
-                    hhq_update(st, __builtin_bit_cast(uint64_t, *(const u32x2*)(rp + t * 32)));
-            } else if (live && ch + 1 == my_chunks) {
-                // this stream's last chunk: whole packets, the remainder
-                // packet, the digest; afterwards the quad only passes barriers
-                const uint32_t full = tail / 32;
-#pragma unroll 1
-                for (uint32_t t = 0; t < full; ++t) hhq_update(st, __builtin_bit_cast(uint64_t, *(const u32x2*)(rp + t * 32)));
-                if (tail % 32) hhq_remainder(st, row0 + full * 32, tail % 32, q);
-                finish();
-            }
-        }
+        });
     }
 }
 
@@ -333,31 +269,18 @@ static DecodeMixedPick decode_mixed_entry() {
     return {k_decode_mixed<C, R, spw>, spw, spw + (spw * (C + R) + 15) / 16};
 }
 
-template <int C>
-static DecodeMixedPick pick_decode_mixed_r(int R) {
-    switch (R) {
-        case 0: return decode_mixed_entry<C, 0>();
-        case 1: return decode_mixed_entry<C, 1>();
-        case 2: return decode_mixed_entry<C, 2>();
-        case 3: return decode_mixed_entry<C, 3>();
-        case 4: return decode_mixed_entry<C, 4>();
-    }
-    return {nullptr, 0, 0};
-}
-
 #define RSG_MDEC_CAT2(a, b) a##b
 #define RSG_MDEC_CAT(a, b) RSG_MDEC_CAT2(a, b)
 
+// this part's source counts: C = P + 1 + j*kMdecParts, j = 0..3
 DecodeMixedPick RSG_MDEC_CAT(pick_decode_mixed_part, RSG_MDEC_PART)(int C, int R) {
     constexpr int P = RSG_MDEC_PART;
     static_assert(P >= 0 && P < kMdecParts, "RSG_MDEC_PART");
-    switch ((C - 1 - P) / kMdecParts) {
-        case 0: return pick_decode_mixed_r<P + 1>(R);
-        case 1: return pick_decode_mixed_r<P + 1 + kMdecParts>(R);
-        case 2: return pick_decode_mixed_r<P + 1 + 2 * kMdecParts>(R);
-        case 3: return pick_decode_mixed_r<P + 1 + 3 * kMdecParts>(R);
-    }
-    return {nullptr, 0, 0};
+    return dispatch_int<0, 3>((C - 1 - P) / kMdecParts, DecodeMixedPick{}, [R](auto j) {
+        return dispatch_int<0, mixed::kDecMaxR>(R, DecodeMixedPick{}, [](auto r) {
+            return decode_mixed_entry<P + 1 + decltype(j)::value * kMdecParts, decltype(r)::value>();
+        });
+    });
 }
 
 #else  // the launcher

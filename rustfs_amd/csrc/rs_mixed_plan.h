@@ -14,10 +14,12 @@
 #include <algorithm>
 #include <vector>
 
+#include "rs_fused.h"
+
 namespace rsg {
 namespace mixed {
 
-constexpr uint32_t kChunk = 512;  // bytes per shard per kernel step (kFusedChunk)
+constexpr uint32_t kChunk = kFusedChunk;  // bytes per shard per kernel step
 
 // The caller's descriptor (rsg_stripe_desc, include/rsgpu.h): data shard c at
 // data + data_off + c*shard_len, parity shard r at parity + parity_off + r*shard_len.
@@ -32,16 +34,15 @@ struct MixedDesc {
     uint32_t len, job;
 };
 
-// Stripes per workgroup: the packed kernel's rule (fused_spw_for,
-// rs_kernels.hip): fill the hasher waves, cap LDS.
-constexpr int spw_for(int T) { return (T % 16 == 0) ? 1 : (T % 8 == 0) ? 2 : (T % 4 == 0 || T <= 6) ? 4 : 2; }
+// Stripes per workgroup: the fused kernels' rule (rs_fused.h).
+constexpr int spw_for(int T) { return fused_spw_for(T); }
 
 // Geometries the one-launch kernel is instantiated for (the packed kernel's
 // range); others run the per-length paths.
 constexpr bool kernel_geometry(int k, int m) { return k >= 1 && k <= 16 && m >= 1 && m <= 4; }
 
-// ceil(len / kChunk) without overflow at len = 0xffffffff; 0 for an empty shard
-constexpr uint32_t chunks_of(uint64_t len) { return (uint32_t)(len / kChunk) + (len % kChunk ? 1u : 0u); }
+// a shard's chunk count (rs_fused.h): no overflow at len = 0xffffffff, 0 for an empty shard
+constexpr uint32_t chunks_of(uint64_t len) { return fused_chunks(len); }
 
 // Validation.  data_base / parity_base: the arenas' addresses (equal for an
 // aliased layout such as a3: parity_off = data_off + k*shard_len).  True when

@@ -710,6 +710,46 @@ int enter(rsg_ctx* ctx) {
     if (!ctx) return RSG_ERR_INVALID_ARG;
     return hip_status(hipSetDevice(ctx->device));
 }
+
+// The pipeline slots one host-batch call takes (pipe_mu held throughout).
+struct PipeRun {
+    rsg_ctx* ctx;
+    bool used[rsg_ctx::kPipeSlots] = {};
+
+    // the next slot round-robin, now one of this call's
+    int next_slot() {
+        const int b = (int)(ctx->next_slot++ % rsg_ctx::kPipeSlots);
+        used[b] = true;
+        return b;
+    }
+    // Wait for everything this call queued: after a failed enqueue, earlier
+    // sub-batches' copies still read and write the caller's buffers, and no
+    // copy may outlive a call that returns no ticket.
+    void drain() {
+        for (int b = 0; b < rsg_ctx::kPipeSlots; ++b)
+            if (used[b]) (void)hipStreamSynchronize(ctx->pipe_stream[b]);
+    }
+    // The end of a submit whose enqueues returned st.  Success: one event per
+    // slot used recorded into the job, and the job's ticket.  An error (st, or
+    // an event's): drained, no ticket.
+    int finish(int st, std::shared_ptr<rsg_ctx::Job> job, uint64_t* ticket) {
+        for (int b = 0; b < rsg_ctx::kPipeSlots && !st; ++b) {
+            if (!used[b]) continue;
+            hipEvent_t e;
+            if ((st = hip_status(hipEventCreateWithFlags(&e, hipEventDisableTiming)))) break;
+            job->done.push_back(e);
+            st = hip_status(hipEventRecord(e, ctx->pipe_stream[b]));
+        }
+        if (st) {
+            drain();
+            return st;
+        }
+        *ticket = ctx->next_ticket++;
+        ctx->jobs.emplace(*ticket, std::move(job));
+        return RSG_OK;
+    }
+};
+
 // A free host lane, locked: try every lane once starting round-robin, then
 // wait on the starting one.
 std::unique_lock<std::mutex> acquire_lane(rsg_ctx* ctx, HostLane*& lane) {
@@ -886,6 +926,7 @@ int rsg_encode_batch_host_submit(rsg_ctx* ctx, int k, int m, size_t shard_len, s
     if (want_hash && !hash_key(algo)) return RSG_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(ctx->pipe_mu);
     auto job = std::make_shared<rsg_ctx::Job>();
+    PipeRun run{ctx};
     // nothing to move: parity of m = 0 is empty; digests are still computed
     // (an empty shard hashes to the digest of the empty message)
     const bool work = n > 0 && ((m > 0 && shard_len > 0) || want_hash);
@@ -898,12 +939,10 @@ int rsg_encode_batch_host_submit(rsg_ctx* ctx, int k, int m, size_t shard_len, s
         const uint64_t dig_bytes = want_hash ? chunk * (k + m) * 32 : 0;
         if ((st = ctx->ensure_pipeline((size_t)(chunk * dstride + dig_bytes)))) return st;
         const size_t dpitch_data = (shard_pitch == dpitch) ? (size_t)(k * dpitch) : 0;
-        bool used[rsg_ctx::kPipeSlots] = {};
         const int fail_at = ctx->fail_subbatch.load();  // rsg_test_fail_subbatch (tests only)
         int sub = 0;
         for (uint64_t s0 = 0; s0 < n && !st; s0 += chunk, ++sub) {
-            const int b = (int)(ctx->next_slot++ % rsg_ctx::kPipeSlots);
-            used[b] = true;
+            const int b = run.next_slot();
             hipStream_t s = ctx->pipe_stream[b];
             const uint64_t cnt = std::min<uint64_t>(chunk, n - s0);
             uint8_t* hbase = h_stripes + s0 * stripe_stride;
@@ -927,32 +966,12 @@ int rsg_encode_batch_host_submit(rsg_ctx* ctx, int k, int m, size_t shard_len, s
                 st = hip_status(hipMemcpyAsync(h_digests + s0 * (k + m) * 32, ddig, cnt * (k + m) * 32,
                                                hipMemcpyDeviceToHost, s));
         }
-        if (st) {
-            // An enqueue failed after earlier sub-batches were queued: their
-            // copies still read h_stripes and write parity / digests into the
-            // caller's buffers.  Drain every slot this job used before
-            // returning the error, so no copy outlives the call (the caller
-            // gets no ticket and may free the buffers at once).
-            for (int b = 0; b < rsg_ctx::kPipeSlots; ++b)
-                if (used[b]) (void)hipStreamSynchronize(ctx->pipe_stream[b]);
-            return st;
-        }
-        for (int b = 0; b < rsg_ctx::kPipeSlots && !st; ++b) {
-            if (!used[b]) continue;
-            hipEvent_t e;
-            if ((st = hip_status(hipEventCreateWithFlags(&e, hipEventDisableTiming)))) break;
-            job->done.push_back(e);
-            st = hip_status(hipEventRecord(e, ctx->pipe_stream[b]));
-        }
-        if (st) {  // no ticket: drain the queued sub-batches here (as above)
-            for (int b = 0; b < rsg_ctx::kPipeSlots; ++b)
-                if (used[b]) (void)hipStreamSynchronize(ctx->pipe_stream[b]);
-            return st;
-        }
     }
-    *ticket = ctx->next_ticket++;
-    ctx->jobs.emplace(*ticket, std::move(job));
-    return RSG_OK;
+    // An enqueue that failed after earlier sub-batches were queued: no ticket,
+    // and their copies (they read h_stripes and write parity / digests into
+    // the caller's buffers) have finished, so the caller may free the buffers
+    // at once.
+    return run.finish(st, std::move(job), ticket);
 }
 
 namespace {
@@ -2214,17 +2233,16 @@ int rsg_encode_mixed_host_submit(rsg_ctx* ctx, int k, int m, size_t n, const rsg
     }
     std::lock_guard<std::mutex> g(ctx->pipe_mu);
     auto job = std::make_shared<rsg_ctx::Job>();
+    PipeRun run{ctx};
     const bool work = n > 0 && (m > 0 || want_hash);
     if (work) {
         uint64_t need = RSG_MIXED_STAGE_BYTES;  // a stripe larger than that grows the stage
         for (const auto& b : subs) need = std::max(need, rsg::mixed::stage_bytes(b, k, m, want_hash));
         if ((st = ctx->ensure_pipeline((size_t)need))) return st;
-        bool used[rsg_ctx::kPipeSlots] = {};
         const int fail_at = ctx->fail_subbatch.load();  // rsg_test_fail_subbatch (tests only)
         int sub = 0;
         for (const auto& b : subs) {
-            const int slot = (int)(ctx->next_slot++ % rsg_ctx::kPipeSlots);
-            used[slot] = true;
+            const int slot = run.next_slot();
             hipStream_t s = ctx->pipe_stream[slot];
             const uint64_t dspan = b.data_hi - b.data_lo, pspan = b.parity_hi - b.parity_lo;
             uint8_t* dd = ctx->d_stage[slot];
@@ -2240,24 +2258,9 @@ int rsg_encode_mixed_host_submit(rsg_ctx* ctx, int k, int m, size_t n, const rsg
             if (st) break;
             ++sub;
         }
-        for (int b = 0; b < rsg_ctx::kPipeSlots && !st; ++b) {
-            if (!used[b]) continue;
-            hipEvent_t e;
-            if ((st = hip_status(hipEventCreateWithFlags(&e, hipEventDisableTiming)))) break;
-            job->done.push_back(e);
-            st = hip_status(hipEventRecord(e, ctx->pipe_stream[b]));
-        }
-        if (st) {
-            // no ticket: drain every slot this job used before returning, so
-            // no copy outlives the call (rsg_encode_batch_host_submit's contract)
-            for (int b = 0; b < rsg_ctx::kPipeSlots; ++b)
-                if (used[b]) (void)hipStreamSynchronize(ctx->pipe_stream[b]);
-            return st;
-        }
     }
-    *ticket = ctx->next_ticket++;
-    ctx->jobs.emplace(*ticket, std::move(job));
-    return RSG_OK;
+    // on an error no ticket and no copy outlives the call (rsg_encode_batch_host_submit's contract)
+    return run.finish(st, std::move(job), ticket);
 }
 
 int rsg_encode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe_desc* h_desc, const uint8_t* h_data,
@@ -2507,10 +2510,11 @@ int rsg_decode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record
     } else if ((st = hip_status(hipMalloc((void**)&own.d, (size_t)need)))) {
         return st;
     }
+    PipeRun run{ctx};
     std::vector<uint32_t> masks;
     for (const auto& b : subs) {
         // one slot at a time: a sub-batch's verdicts decide what comes back
-        const int slot = slots ? (int)(ctx->next_slot++ % rsg_ctx::kPipeSlots) : 0;
+        const int slot = slots ? run.next_slot() : 0;
         hipStream_t s = slots ? ctx->pipe_stream[slot] : nullptr;
         uint8_t* stage = slots ? ctx->d_stage[slot] : own.d;
         const uint64_t rspan = b.rec_hi - b.rec_lo, ospan = b.out_hi - b.out_lo;

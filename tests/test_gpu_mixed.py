@@ -23,7 +23,7 @@ _REF = {}
 
 
 def spw_for(t):
-    """Stripes per workgroup of the kernel (rs_mixed_plan.h spw_for)."""
+    """Stripes per workgroup of the kernel (rs_fused.h fused_spw_for)."""
     return 1 if t % 16 == 0 else 2 if t % 8 == 0 else 4 if (t % 4 == 0 or t <= 6) else 2
 
 

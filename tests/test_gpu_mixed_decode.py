@@ -21,7 +21,7 @@ _REF = {}
 
 
 def spw_for(t):
-    """Stripes per workgroup of the kernel for t rows (rs_mixed_decode_plan.h decode_spw_for)."""
+    """Stripes per workgroup of the kernel for t rows (rs_mixed_decode_plan.h decode_spw_for over rs_fused.h fused_spw_for)."""
     return 2 if t >= 20 else 1 if t % 16 == 0 else 2 if t % 8 == 0 else 4 if (t % 4 == 0 or t <= 6) else 2
 
 
