@@ -440,7 +440,8 @@ int rsg_encode_mixed_host_submit(rsg_ctx *ctx, int k, int m, size_t n, const rsg
  * plans read, and copies back only the out windows of shards it rebuilt. */
 typedef struct rsg_record_desc {
     uint64_t rec_off;   /* shard i's record of this stripe at files[i] + rec_off */
-    uint64_t out_off;   /* a rebuilt data shard c is written to out + out_off + c*shard_len */
+    uint64_t out_off;   /* a rebuilt data shard c is written to out + out_off + c*shard_len
+                           (rsg_heal_mixed_*: target i's record at targets[i] + out_off) */
     uint32_t shard_len; /* 0: the records are bare digests of the empty message */
     uint32_t present;   /* bit i set: shard i's record of this stripe may be read (i < k+m) */
 } rsg_record_desc;
@@ -450,6 +451,67 @@ int rsg_decode_mixed_dev(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_
 int rsg_decode_mixed_host(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_desc *h_desc,
                           const uint8_t *const *h_files, int algo, int verify_surplus, uint8_t *h_out,
                           uint32_t *h_served, int *h_status);
+
+/* ---- mixed-length batch heal: rebuild the target shards' records of n unrelated stripes ----
+ * The third mixed-length path: Erasure::heal (heal.rs:112-206), which calls
+ * decode_data_and_parity (erasure.rs:917) per block and writes the healed
+ * shards through BitrotWriter (bitrot.rs:139-247), over stripes whose shard
+ * lengths, sets of present shards and rot all differ: every block, full or
+ * short, of every object on a replaced disk in one call.  The contract is
+ * rsg_heal_records_dev's, applied per stripe.
+ * files: k+m record arenas as in rsg_decode_mixed_dev (a NULL arena means
+ * shard i is absent for every stripe, whatever `present` says); a source
+ * record of stripe s (h_desc[s], rsg_record_desc, a host array the call does
+ * not keep) is at files[i] + rec_off.  targets: k+m pointers; targets[i] !=
+ * NULL marks shard i, data or parity, as a heal target for every stripe of the
+ * call: its record [HH256S][shard_len bytes] of stripe s is written at
+ * targets[i] + out_off.  A target shard is never read: files[i] and bit i of
+ * `present` are ignored for it.  shard_len == 0 touches no body; the target
+ * record is the bare digest of the empty message.
+ * Every record used is hashed and compared with its header first; a
+ * mismatching record counts as absent for that stripe only, and the stripe is
+ * run again under the reduced set, at most k+m rounds, exactly as the GET does.
+ * The targets are computed from the first k verified non-target shards in
+ * ascending index; every verified source past those is re-derived and compared
+ * byte for byte (heal.rs:180-196).
+ * h_status[s]: RSG_OK, RSG_ERR_TOO_FEW_SHARDS (fewer than k verified sources;
+ * more targets than m gives it for every stripe) or
+ * RSG_ERR_INCONSISTENT_SOURCES.  Target records of a failed stripe carry an
+ * all-zero 32-byte header (they never verify) and unspecified bodies.
+ * algo: HIGHWAY256S or HIGHWAY256S_LEGACY.  Both forms are synchronous.
+ * No source byte is written.
+ * RSG_ERR_INVALID_ARG with nothing written: no target at all; a NULL pointer;
+ * an unknown algo; a `present` bit at or above k+m; record ranges [rec_off,
+ * +32+shard_len) or target ranges [out_off, +32+shard_len) not strictly
+ * ascending and disjoint in list order (a zero-length stripe's range is its 32
+ * header bytes); a range that wraps the address space; a target's span (first
+ * range's start to last range's end) meeting the record span of an arena that
+ * is read, or another target's span.  m == 0 is RSG_ERR_ZERO_PARITY_SHARDS,
+ * k+m > 32 RSG_ERR_UNSUPPORTED, other geometry errors as rsg_check_geometry;
+ * n == 0 is RSG_OK.
+ * k <= 16 with m <= 4 run one launch per distinct set of readable shards, and
+ * again for the stripes in which a record failed its hash; the headers of
+ * failed stripes are zeroed in one small launch after the last round.  Other
+ * geometries give the same results through rsg_heal_records_dev, stripe by
+ * stripe; there a stripe with shard_len == 0 is judged by `present` alone.
+ *
+ * rsg_heal_mixed_dev: device arenas; runs on `stream` and waits for it.  No
+ * byte of a target arena outside the stripes' target ranges is written.
+ *
+ * rsg_heal_mixed_host: host arenas, page-locked or pageable.  Consecutive
+ * stripes are taken into sub-batches that fit RSG_MIXED_STAGE_BYTES of the
+ * host-batch staging slots (a larger stripe gets a sub-batch of its own); a
+ * sub-batch copies up the record span of every arena that some stripe of it
+ * may read and copies back, once per target, its target span (first target
+ * range's start to last one's end): the bytes of the span between target
+ * ranges are overwritten with unspecified values, as in
+ * rsg_encode_mixed_host, so pack the target arenas densely. */
+int rsg_heal_mixed_dev(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_desc *h_desc,
+                       const uint8_t *const *d_files, uint8_t *const *d_targets, int algo,
+                       int *h_status, void *stream);
+int rsg_heal_mixed_host(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_desc *h_desc,
+                        const uint8_t *const *h_files, uint8_t *const *h_targets, int algo,
+                        int *h_status);
 
 /* Page-lock / release host memory for DMA (hipHostRegister). */
 int rsg_pin(void *ptr, size_t bytes);

@@ -65,7 +65,7 @@ EXPORTED = (
     "rsg_set_record_engine", "rsg_decode_records_into_dev", "rsg_decode_records_submit",
     "rsg_heal_records_submit", "rsg_test_fail_subbatch", "rsg_set_tuning", "rsg_get_tuning",
     "rsg_encode_mixed_dev", "rsg_encode_mixed_host", "rsg_encode_mixed_host_submit",
-    "rsg_decode_mixed_dev", "rsg_decode_mixed_host",
+    "rsg_decode_mixed_dev", "rsg_decode_mixed_host", "rsg_heal_mixed_dev", "rsg_heal_mixed_host",
 )
 
 # Staging bytes per sub-batch of rsg_encode_mixed_host (include/rsgpu.h)
@@ -158,6 +158,8 @@ def load():
         L.rsg_encode_mixed_host_submit.argtypes = [P, I, I, S, P, P, P, P, I, ctypes.POINTER(ctypes.c_uint64)]
         L.rsg_decode_mixed_dev.argtypes = [P, I, I, S, P, P, I, I, P, P, P, P]
         L.rsg_decode_mixed_host.argtypes = [P, I, I, S, P, P, I, I, P, P, P]
+        L.rsg_heal_mixed_dev.argtypes = [P, I, I, S, P, P, P, I, P, P]
+        L.rsg_heal_mixed_host.argtypes = [P, I, I, S, P, P, P, I, P]
         _lib = L
         return L
 

@@ -1,10 +1,12 @@
 // rs_mixed.h — launchers of the mixed-length kernels: the fused encode +
 // HH256S (rs_mixed.hip) and the verify + rebuild of record stripes
-// (rs_mixed_decode.hip); internal to librsgpu.
+// (rs_mixed_decode.hip) and their heal (rs_mixed_heal.hip); internal to
+// librsgpu.
 #pragma once
 
 #include "rs_kernels.h"
 #include "rs_mixed_decode_plan.h"
+#include "rs_mixed_heal_plan.h"
 #include "rs_mixed_plan.h"
 
 namespace rsg {
@@ -48,5 +50,33 @@ struct DecodeMixedParams {
 // mixed::decode_kernel_geometry(C, R) shapes only.
 hipError_t launch_decode_mixed(const DecodeMixedParams& p, const mixed::DecDesc* d_desc, uint64_t n,
                                hipStream_t stream);
+
+// Kernel arguments of k_heal_mixed<C,R,SPW>: one launch serves the stripes of
+// one mask group, which share the heal plan.  Row c < C is source c of the
+// plan; row C + r belongs to computed row r: rows r < e are the heal targets
+// (the record [digest][shard] of stripe j is written at target[r] + out_off of
+// its descriptor, nothing is read for them), rows r >= e re-derive the surplus
+// shard whose records lie in file[C + r] and compare.
+struct HealMixedParams {
+    const uint8_t* file[mixed::kDecMaxC + mixed::kDecMaxR];  // row -> record arena (null: not read)
+    uint8_t* target[mixed::kDecMaxR];                        // computed row r < e -> target arena
+    uint8_t* flags;      // [jobs][fstride]: flags[job*fstride + row] = 1 verified, 0 not, for every row read
+    uint32_t* mismatch;  // [jobs]: nonzero where a re-derived surplus row differs from its record
+    uint64_t key[4];
+    uint32_t tab[mixed::kDecMaxR][mixed::kDecMaxC][5];  // v_perm tables of computed row r over source c
+    uint32_t C, R, e, fstride;
+};
+
+// One launch over the n stripes of d_desc (planner order).
+// mixed::heal_kernel_shape(C, R) shapes only, 1 <= e <= R.
+hipError_t launch_heal_mixed(const HealMixedParams& p, const mixed::DecDesc* d_desc, uint64_t n, hipStream_t stream);
+
+// All-zero 32-byte headers at target[t] + d_offs[s] for every t < nt, s < n
+// (the target records of failed stripes), any alignment, one launch.
+struct HealZeroParams {
+    uint8_t* target[32];
+    uint32_t nt;
+};
+hipError_t launch_heal_zero_headers(const HealZeroParams& p, const uint64_t* d_offs, uint64_t n, hipStream_t stream);
 
 }  // namespace rsg

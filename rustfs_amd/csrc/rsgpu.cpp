@@ -2554,6 +2554,314 @@ int rsg_decode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record
     return RSG_OK;
 }
 
+}  // extern "C"
+
+// ---- mixed-length batch heal (rs_mixed_heal.hip, rs_mixed_heal_plan.h) ----
+
+namespace {
+
+// The kernel's arguments for one mask group: sources, then the targets' and
+// the surplus shards' coefficient rows (plan_row over the codec's DecodePlan
+// of the readable non-target shards).
+int heal_mixed_params(Codec* cd, int k, int m, uint32_t mask, const rsg::mixed::HealPlan& hp,
+                      const uint8_t* const* d_files, uint8_t* const* d_targets, const uint64_t* key, uint8_t* d_flags,
+                      uint32_t* d_mismatch, rsg::HealMixedParams& p, int* row_shard) {
+    std::memset(&p, 0, sizeof(p));
+    const int e = (int)hp.tgt.size(), R = hp.rows();
+    if (!rsg::mixed::heal_kernel_shape(k, R) || e < 1) return RSG_ERR_UNSUPPORTED;
+    p.C = (uint32_t)k;
+    p.R = (uint32_t)R;
+    p.e = (uint32_t)e;
+    p.fstride = (uint32_t)(k + m);
+    p.flags = d_flags;
+    p.mismatch = d_mismatch;
+    std::memcpy(p.key, key, sizeof(p.key));
+    for (int c = 0; c < k; ++c) {
+        p.file[c] = d_files[hp.src[c]];
+        row_shard[c] = hp.src[c];
+    }
+    std::vector<uint8_t> present((size_t)(k + m), 0);
+    for (int i = 0; i < k + m; ++i) present[i] = (mask >> i & 1u) ? 1 : 0;
+    std::shared_ptr<DecodePlan> plan = cd->plan(present.data());
+    if (!plan) return RSG_ERR_TOO_FEW_SHARDS;
+    std::vector<uint8_t> row((size_t)k);
+    for (int r = 0; r < R; ++r) {
+        const int shard = r < e ? hp.tgt[r] : hp.surplus[r - e];
+        if (r < e) {
+            p.target[r] = d_targets[shard];
+            row_shard[k + r] = -1;
+        } else {
+            p.file[k + r] = d_files[shard];
+            row_shard[k + r] = shard;
+        }
+        plan_row(*cd, *plan, shard, row.data());
+        for (int c = 0; c < k; ++c) coef_tables(row[c], p.tab[r][c]);
+    }
+    return RSG_OK;
+}
+
+// Stripes d[0 .. count) of a validated list on stream s, to the end (the
+// stream is waited for): shard i's record of stripe j at d_files[i] +
+// d[j].rec_off - rec_lo (d_files[i] null: absent), target i's record at
+// d_targets[i] + d[j].out_off - out_lo (non-null: a target, never read).
+// Failed stripes end with all-zero target headers.
+int heal_mixed_run(rsg_ctx* ctx, int k, int m, const rsg::mixed::RecordDesc* d, size_t count, uint64_t rec_lo,
+                   uint64_t out_lo, const uint8_t* const* d_files, uint8_t* const* d_targets, int algo, int* h_status,
+                   hipStream_t s) {
+    namespace mx = rsg::mixed;
+    if (count == 0) return RSG_OK;
+    const int T = k + m;
+    uint64_t bases[32] = {}, tbases[32] = {};
+    for (int i = 0; i < T; ++i) {
+        bases[i] = (uint64_t)(uintptr_t)d_files[i];
+        tbases[i] = (uint64_t)(uintptr_t)d_targets[i];
+    }
+    const uint32_t targets = mx::arena_mask(T, tbases);
+    const uint32_t arenas = mx::arena_mask(T, bases) & ~targets;
+    std::vector<uint32_t> masks(count);
+    for (size_t j = 0; j < count; ++j) masks[j] = d[j].present & arenas;
+    int st = RSG_OK;
+
+    if (mx::heal_kernel_geometry(k, m)) {
+        std::shared_ptr<Codec> cd = get_codec(k, m);
+        if (!cd) return RSG_ERR_INVALID_ARG;
+        const uint64_t* key = hash_key(algo);
+        const size_t fbytes = (size_t)mx::stage_round((uint64_t)count * T);
+        const size_t mbytes = (size_t)mx::stage_round((uint64_t)count * 4);
+        const size_t obytes = (size_t)mx::stage_round((uint64_t)count * 8);
+        const size_t tbytes = count * sizeof(mx::DecDesc);
+        std::unique_ptr<rsg_ctx::MixedTab> mt = ctx->take_mixed_tab();
+        if (!mt) return RSG_ERR_DEVICE;
+        if ((st = mt->buf.ensure(fbytes + mbytes + obytes + tbytes, fbytes + mbytes + obytes + tbytes))) return st;
+        uint8_t* d_flags = mt->buf.d;
+        uint32_t* d_mis = (uint32_t*)(mt->buf.d + fbytes);
+        uint8_t* d_offs = mt->buf.d + fbytes + mbytes;
+        uint8_t* d_tab = d_offs + obytes;
+        const uint8_t* h_flags = mt->buf.h;
+        const uint32_t* h_mis = (const uint32_t*)(mt->buf.h + fbytes);
+        uint64_t* h_offs = (uint64_t*)(mt->buf.h + fbytes + mbytes);
+        uint8_t* h_tab = mt->buf.h + fbytes + mbytes + obytes;
+        st = hip_status(hipMemsetAsync(d_mis, 0, mbytes, s));
+
+        std::vector<uint32_t> todo(count), redo;
+        for (size_t j = 0; j < count; ++j) todo[j] = (uint32_t)j;
+        std::vector<mx::MaskGroup> groups;
+        std::vector<mx::DecDesc> tab;
+        std::vector<uint8_t> flags((size_t)count * T, 1);  // by shard
+        mx::HealPlan hp;
+        struct Launch {
+            rsg::HealMixedParams p;
+            size_t at, n;
+            int row_shard[mx::kDecMaxC + mx::kDecMaxR];
+        };
+        std::vector<Launch> launches;
+        while (!st && !todo.empty()) {
+            mx::group_by_mask(masks.data(), todo, groups);
+            launches.clear();
+            size_t at = 0;
+            for (const mx::MaskGroup& g : groups) {
+                if (!mx::plan_heal_mask(k, m, g.mask, targets, hp)) continue;  // TOO_FEW: no launch
+                launches.emplace_back();
+                Launch& l = launches.back();
+                if ((st = heal_mixed_params(cd.get(), k, m, g.mask, hp, d_files, d_targets, key, d_flags, d_mis, l.p,
+                                            l.row_shard)))
+                    break;
+                mx::order_heal_group_for_kernel(d, g.stripes, 0, rec_lo, out_lo, tab);
+                std::memcpy(h_tab + at * sizeof(mx::DecDesc), tab.data(), tab.size() * sizeof(mx::DecDesc));
+                l.at = at;
+                l.n = tab.size();
+                at += tab.size();
+            }
+            if (st || launches.empty()) break;
+            st = hip_status(hipMemcpyAsync(d_tab, h_tab, at * sizeof(mx::DecDesc), hipMemcpyHostToDevice, s));
+            for (size_t i = 0; i < launches.size() && !st; ++i)
+                st = hip_status(rsg::launch_heal_mixed(
+                    launches[i].p, (const mx::DecDesc*)(d_tab + launches[i].at * sizeof(mx::DecDesc)), launches[i].n, s));
+            if (!st) st = hip_status(hipMemcpyAsync(mt->buf.h, mt->buf.d, fbytes + mbytes, hipMemcpyDeviceToHost, s));
+            if (!st) st = hip_status(hipStreamSynchronize(s));
+            if (st) break;
+            // the kernel's flags are by row: to shard indices, for the planner
+            size_t li = 0;
+            for (const mx::MaskGroup& g : groups) {
+                if (!mx::plan_heal_mask(k, m, g.mask, targets, hp)) continue;
+                const Launch& l = launches[li++];
+                for (uint32_t j : g.stripes)
+                    for (int row = 0; row < (int)(l.p.C + l.p.R); ++row)
+                        if (l.row_shard[row] >= 0)
+                            flags[(size_t)j * T + l.row_shard[row]] = h_flags[(size_t)j * T + row];
+            }
+            mx::redo_heal_from_flags(k, m, targets, groups, 0, flags.data(), (size_t)T, masks.data(), redo);
+            todo.swap(redo);
+        }
+        // verdicts; the failed stripes' target headers zeroed in one launch
+        // (a first round may already have written a digest there)
+        size_t nfail = 0;
+        if (!st) {
+            for (size_t j = 0; j < count; ++j) {
+                h_status[j] = mx::popcount32(masks[j]) < k ? RSG_ERR_TOO_FEW_SHARDS
+                              : h_mis[j]                   ? RSG_ERR_INCONSISTENT_SOURCES
+                                                           : RSG_OK;
+                if (h_status[j] != RSG_OK) h_offs[nfail++] = d[j].out_off - out_lo;
+            }
+        }
+        if (!st && nfail) {
+            rsg::HealZeroParams z;
+            std::memset(&z, 0, sizeof(z));
+            for (int i = 0; i < T; ++i)
+                if (d_targets[i]) z.target[z.nt++] = d_targets[i];
+            st = hip_status(hipMemcpyAsync(d_offs, h_offs, nfail * 8, hipMemcpyHostToDevice, s));
+            if (!st) st = hip_status(rsg::launch_heal_zero_headers(z, (const uint64_t*)d_offs, nfail, s));
+            if (!st) st = hip_status(hipStreamSynchronize(s));
+        }
+        if (st) (void)hipStreamSynchronize(s);
+        ctx->give_mixed_tab(std::move(mt), s);
+        return st;
+    }
+    // m > 4 or k > 16: the per-length engine, stripe by stripe (it zeroes the
+    // headers of a stripe it fails); an empty stripe is judged by its mask
+    std::vector<const uint8_t*> fp((size_t)T);
+    std::vector<uint8_t*> tg((size_t)T);
+    for (size_t j = 0; j < count; ++j) {
+        const uint64_t len = d[j].shard_len;
+        for (int i = 0; i < T; ++i) {
+            fp[i] = (masks[j] >> i & 1u) ? d_files[i] + (d[j].rec_off - rec_lo) : nullptr;
+            tg[i] = d_targets[i] ? d_targets[i] + (d[j].out_off - out_lo) : nullptr;
+        }
+        if (len) {
+            if ((st = rsg_heal_records_dev(ctx, k, m, (size_t)len, 1, fp.data(), tg.data(), algo, nullptr, &h_status[j],
+                                           s)))
+                return st;
+            continue;
+        }
+        const bool ok = mx::popcount32(masks[j]) >= k && mx::popcount32(targets) <= m;
+        h_status[j] = ok ? RSG_OK : RSG_ERR_TOO_FEW_SHARDS;
+        for (int i = 0; i < T && !st; ++i) {
+            if (!tg[i]) continue;
+            st = ok ? hash_messages(algo, tg[i], 0, 1, 1, 0, 0, tg[i], s) : hip_status(hipMemsetAsync(tg[i], 0, 32, s));
+        }
+        if (st) return st;
+    }
+    return hip_status(hipStreamSynchronize(s));
+}
+
+// Argument checks shared by the device and host forms.
+int heal_mixed_check(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_desc* h_desc, const uint8_t* const* files,
+                     uint8_t* const* targets, int algo, const int* h_status) {
+    int st = enter(ctx);
+    if (st) return st;
+    if ((st = check_geometry(k, m))) return st;
+    if (m == 0) return RSG_ERR_ZERO_PARITY_SHARDS;
+    if (!hash_key(algo)) return RSG_ERR_INVALID_ARG;
+    if (n == 0) return RSG_OK;
+    if (k + m > 32) return RSG_ERR_UNSUPPORTED;
+    if (!h_desc || !files || !targets || !h_status || n > 0x7fffffffull) return RSG_ERR_INVALID_ARG;
+    uint64_t bases[32] = {}, tbases[32] = {};
+    for (int i = 0; i < k + m; ++i) {
+        bases[i] = (uint64_t)(uintptr_t)files[i];
+        tbases[i] = (uint64_t)(uintptr_t)targets[i];
+    }
+    if (!rsg::mixed::validate_heal(k, m, n, reinterpret_cast<const rsg::mixed::RecordDesc*>(h_desc), bases, tbases))
+        return RSG_ERR_INVALID_ARG;
+    return RSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsg_heal_mixed_dev(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_desc* h_desc,
+                       const uint8_t* const* d_files, uint8_t* const* d_targets, int algo, int* h_status,
+                       void* stream) {
+    int st = heal_mixed_check(ctx, k, m, n, h_desc, d_files, d_targets, algo, h_status);
+    if (st || n == 0) return st;
+    return heal_mixed_run(ctx, k, m, reinterpret_cast<const rsg::mixed::RecordDesc*>(h_desc), n, 0, 0, d_files,
+                          d_targets, algo, h_status, pick_stream(ctx, stream));
+}
+
+int rsg_heal_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_desc* h_desc,
+                        const uint8_t* const* h_files, uint8_t* const* h_targets, int algo, int* h_status) {
+    namespace mx = rsg::mixed;
+    int st = heal_mixed_check(ctx, k, m, n, h_desc, h_files, h_targets, algo, h_status);
+    if (st || n == 0) return st;
+    const mx::RecordDesc* desc = reinterpret_cast<const mx::RecordDesc*>(h_desc);
+    const int T = k + m;
+    int nt = 0, nf = 0;  // targets; arenas that may be read
+    for (int i = 0; i < T; ++i) {
+        if (h_targets[i]) ++nt;
+        else if (h_files[i]) ++nf;
+    }
+    std::vector<mx::HealSubBatch> subs;
+    mx::split_heal(nf, nt, n, desc, RSG_MIXED_STAGE_BYTES, n, subs);
+    uint64_t need = RSG_MIXED_STAGE_BYTES;  // a stripe larger than that grows the stage
+    for (const auto& b : subs) need = std::max(need, mx::heal_stage_bytes(b, nf, nt));
+    // As rsg_decode_mixed_host: the kernel's geometries stage through the
+    // host-batch slots (pipe_mu held to the end: the call is synchronous); the
+    // per-length engine keeps its own tickets under pipe_mu, so the other
+    // geometries stage through a buffer of the call's own on the null stream.
+    const bool slots = mx::heal_kernel_geometry(k, m);
+    std::unique_lock<std::mutex> g(ctx->pipe_mu, std::defer_lock);
+    struct Own {
+        uint8_t* d = nullptr;
+        ~Own() {
+            if (d) (void)hipFree(d);
+        }
+    } own;
+    if (slots) {
+        g.lock();
+        if ((st = ctx->ensure_pipeline((size_t)need))) return st;
+    } else if ((st = hip_status(hipMalloc((void**)&own.d, (size_t)need)))) {
+        return st;
+    }
+    PipeRun run{ctx};
+    const int fail_at = ctx->fail_subbatch.load();  // rsg_test_fail_subbatch (tests only)
+    int sub = 0;
+    for (const auto& b : subs) {
+        // A sub-batch's verdicts need its stream waited for (heal_mixed_run);
+        // its copies back then overlap the next sub-batch on the next slot.
+        const int slot = slots ? run.next_slot() : 0;
+        hipStream_t s = slots ? ctx->pipe_stream[slot] : nullptr;
+        uint8_t* stage = slots ? ctx->d_stage[slot] : own.d;
+        const uint64_t rspan = b.rec_hi - b.rec_lo, ospan = b.out_hi - b.out_lo;
+        uint32_t may = 0;  // arenas some stripe of the sub-batch may read
+        for (size_t j = 0; j < b.count; ++j) may |= desc[b.first + j].present;
+        const uint8_t* dfiles[32] = {};
+        uint8_t* dtargets[32] = {};
+        uint8_t* at = stage;
+        for (int i = 0; i < T && !st; ++i) {
+            if (h_targets[i] || !h_files[i] || !(may >> i & 1u)) continue;
+            dfiles[i] = at;
+            st = hip_status(hipMemcpyAsync(at, h_files[i] + b.rec_lo, rspan, hipMemcpyHostToDevice, s));
+            at += mx::stage_round(rspan);
+        }
+        at = stage + (uint64_t)nf * mx::stage_round(rspan);
+        for (int i = 0; i < T; ++i) {
+            if (!h_targets[i]) continue;
+            dtargets[i] = at;
+            at += mx::stage_round(ospan);
+        }
+        if (!st && sub++ == fail_at) st = RSG_ERR_DEVICE;  // fault injection (tests only)
+        if (!st)
+            st = heal_mixed_run(ctx, k, m, desc + b.first, b.count, b.rec_lo, b.out_lo, dfiles, dtargets, algo,
+                                h_status + b.first, s);
+        // back: the target span of every target, whole (failed stripes' headers are zero in it)
+        for (int i = 0; i < T && !st; ++i)
+            if (h_targets[i])
+                st = hip_status(hipMemcpyAsync(h_targets[i] + b.out_lo, dtargets[i], ospan, hipMemcpyDeviceToHost, s));
+        if (!slots) {
+            const int sy = hip_status(hipStreamSynchronize(s));
+            if (!st) st = sy;
+        }
+        if (st) break;
+    }
+    // nothing of the call is in flight when it returns, whatever its status
+    for (int b = 0; slots && b < rsg_ctx::kPipeSlots; ++b) {
+        if (!run.used[b]) continue;
+        const int sy = hip_status(hipStreamSynchronize(ctx->pipe_stream[b]));
+        if (!st) st = sy;
+    }
+    return st;
+}
+
 int rsg_set_kernel_timing(rsg_ctx* ctx, int on) {
     int st = enter(ctx);
     if (st) return st;

@@ -547,6 +547,79 @@ class Erasure:
             1 if verify_surplus else 0, out.ctypes.data, served, status), "mixed-length decode failed")
         return _lib.status_list(status, n), list(served[:n])
 
+    def _heal_desc(self, desc, file_lens: Sequence[Optional[int]], target_lens: Sequence[Optional[int]]) -> np.ndarray:
+        """The rsg_record_desc array of a mixed-length heal: _record_desc's
+        forms, with out_off the offset of the stripe's record in every target
+        arena; every stripe is checked against the source arenas it may read
+        (a target's source arena is never read) and against every target arena
+        before anything reaches the library."""
+        t = self.total_shard_count()
+        if len(target_lens) != t:
+            raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT, f"invalid shard count: got {len(target_lens)} targets")
+        if len(file_lens) == t:
+            file_lens = [None if target_lens[i] is not None else n for i, n in enumerate(file_lens)]
+        d = self._record_desc(desc, file_lens, 1 << 128)  # the out check is the targets' own, below
+        if d.size:
+            out_end = (d["out_off"].astype(object) + 32 + d["shard_len"].astype(object)).max()
+            for i, n in enumerate(target_lens):
+                if n is not None and out_end > n:
+                    raise RsgError(_lib.RSG_ERR_INVALID_ARG, f"mixed-length record outside target arena {i}")
+        return d
+
+    def heal_mixed(self, files: Sequence, targets: Sequence, desc, algo: int = _lib.RSG_HASH_HIGHWAY256S,
+                   stream=None) -> List[int]:
+        """Mixed-length batch heal on the device (rsg_heal_mixed_dev):
+        `files[i]` is shard i's record arena (a contiguous cuda uint8 tensor,
+        or None: absent for every stripe), `targets[i]` is not None where
+        shard i is a heal target (never read, whatever files[i] and `present`
+        say); `desc` lists per stripe [rec_off, out_off, shard_len, present].
+        Every source record used is verified against its 32-byte header first;
+        target i receives the stripe's record [HH256S][shard_len] at
+        targets[i] + out_off.  Returns the per-stripe rsg_status list; a failed
+        stripe's target records carry an all-zero header.  Synchronous."""
+        t = self.total_shard_count()
+        live = [a for a in list(files) + list(targets) if a is not None]
+        for a in live:
+            if a.dtype.__str__() != "torch.uint8" or not a.is_cuda or not a.is_contiguous():
+                raise TypeError("arenas and targets must be contiguous cuda uint8 tensors")
+        d = self._heal_desc(desc, [f.numel() if f is not None else None for f in files],
+                            [g.numel() if g is not None else None for g in targets])
+        if not live:
+            raise RsgError(_lib.RSG_ERR_INVALID_ARG, "mixed-length heal without arenas")
+        n = d.size
+        status = (ctypes.c_int * max(n, 1))()
+        fp = (ctypes.c_void_p * t)(*[f.data_ptr() if f is not None else None for f in files])
+        tp = (ctypes.c_void_p * t)(*[g.data_ptr() if g is not None else None for g in targets])
+        check(_lib.load().rsg_heal_mixed_dev(
+            _lib.context(_device_of(live[0])).handle, self.data_shards, self.parity_shards, n, d.ctypes.data, fp, tp,
+            algo, status, _stream_of(live[0], stream)), "mixed-length heal failed")
+        return _lib.status_list(status, n)
+
+    def heal_mixed_host(self, files: Sequence, targets: Sequence, desc,
+                        algo: int = _lib.RSG_HASH_HIGHWAY256S) -> List[int]:
+        """heal_mixed on host arenas (rsg_heal_mixed_host): numpy uint8
+        arrays, page-locked or pageable; sub-batches of consecutive stripes go
+        through the host-batch staging slots, and the span of target records
+        of a sub-batch comes back whole into every target (bytes between the
+        records are overwritten: pack the target arenas densely)."""
+        t = self.total_shard_count()
+        for a in [a for a in list(files) + list(targets) if a is not None]:
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or not a.flags.c_contiguous:
+                raise TypeError("arenas and targets must be C-contiguous uint8 arrays")
+        for g in targets:
+            if g is not None:
+                _writable(g)
+        d = self._heal_desc(desc, [f.size if f is not None else None for f in files],
+                            [g.size if g is not None else None for g in targets])
+        n = d.size
+        status = (ctypes.c_int * max(n, 1))()
+        fp = (ctypes.c_void_p * t)(*[f.ctypes.data if f is not None else None for f in files])
+        tp = (ctypes.c_void_p * t)(*[g.ctypes.data if g is not None else None for g in targets])
+        check(_lib.load().rsg_heal_mixed_host(
+            _lib.context(self._device).handle, self.data_shards, self.parity_shards, n, d.ctypes.data, fp, tp, algo,
+            status), "mixed-length heal failed")
+        return _lib.status_list(status, n)
+
     def decode_inline_shards_many(self, objects: Sequence, sizes: Sequence[int],
                                   algo: int = _lib.RSG_HASH_HIGHWAY256S) -> list:
         """The inverse of encode_inline_shards_many: objects[j] is a list of

@@ -23,6 +23,8 @@ what exercises the codec path:
 * HEAL: rebuild the shard files of replaced disks (Erasure::heal,
   heal.rs:112-206) — full blocks in one rsg_heal_records_dev call, the tail
   block through decode_data_and_parity — byte-identical to what PUT wrote.
+  heal_objects heals many objects at once: all their blocks, short ones
+  included, are one mixed-length batch (rsg_heal_mixed_host).
 * VERIFY: deep-scan every shard file (bitrot_verify, bitrot.rs:616-655) with
   one rsg_bitrot_verify_dev call.
 
@@ -517,18 +519,107 @@ class LocalErasureSet:
                     raise _lib.InvalidDataError(_lib.RSG_ERR_INCONSISTENT_SOURCES, f"heal {name}")
             for i in targets:
                 out[i] += self.algo.hash_encode(bytes(shards[i])) + bytes(shards[i])
+        self._write_healed(name, meta, out)
+
+    def _write_healed(self, name: str, meta: dict, parts: dict) -> None:
+        """The end of a heal: parts[i] is disk i's healed part file of the
+        version `meta` (as _meta returns it) names."""
         meta = {key: v for key, v in meta.items() if key != "disks"}
-        for i in targets:  # the healed part in the version's directory, then the disk's meta switches to it
+        for i in parts:  # the healed part in the version's directory, then the disk's meta switches to it
             path = self._path(i, name, meta["version"])
             os.makedirs(os.path.dirname(path), exist_ok=True)
             tmp = path + ".heal-tmp"
             with open(tmp, "wb") as f:
-                f.write(bytes(out[i]))
+                f.write(bytes(parts[i]))
             os.replace(tmp, path)
             old = self._disk_version(i, name)
             self._write_meta_file(i, name, meta)
             if old != meta["version"]:
                 self._drop_version(i, name, old)
+
+    def heal_objects(self, names: Sequence[str], targets: List[int], return_exceptions: bool = False) -> list:
+        """Heal of many objects with one call, the third side of put_objects
+        and get_objects: every block of every object, full or short, is one
+        stripe of one mixed-length batch (rsg_heal_mixed_host: verify-before-use
+        of each source record, the targets' shards rebuilt and their bitrot
+        records written in the same pass).  Sources are read as get_objects
+        reads them (the disks in `targets` are never read); the healed part
+        files and per-disk metadata are written exactly as heal_object writes
+        them, and are byte-identical to what PUT wrote.  Entry j of the result
+        is None, or the exception heal_object(names[j], targets) would have
+        raised, with return_exceptions; otherwise the first one is raised
+        after the healthy objects have been written."""
+        e, k, t = self.erasure, self.k, self.k + self.m
+        targets = sorted(set(int(i) for i in targets))
+        results: list = [None] * len(names)
+        metas: List[Optional[dict]] = [None] * len(names)
+        raws: List[Optional[List[Optional[bytes]]]] = [None] * len(names)
+        for j, name in enumerate(names):
+            try:
+                meta = self._meta(name)
+                size = int(meta["size"])
+                fds = self._open_shards(name, size, meta["version"], [i for i in meta["disks"] if i not in targets])
+                raw: List[Optional[bytes]] = []
+                try:
+                    for fd in fds:
+                        raw.append(None if fd is None else os.pread(fd, os.fstat(fd).st_size, 0))
+                finally:
+                    for fd in fds:
+                        if fd is not None:
+                            os.close(fd)
+                metas[j], raws[j] = meta, raw
+            except Exception as ex:  # no metadata, no read quorum on it, an unreadable disk
+                results[j] = ex
+        # one stripe per block, in object order; an object's records lie at
+        # the same offsets in the source arenas and in the target arenas
+        blocks = []
+        file_off, file_len = {}, {}
+        rec_at = 0
+        for j, raw in enumerate(raws):
+            if raw is None:
+                continue
+            size, bs = int(metas[j]["size"]), int(metas[j]["block_size"])
+            file_off[j] = rec_at
+            for b0 in range(0, size, bs):
+                s = calc_shard_size(min(bs, size - b0), k)
+                blocks.append((j, s, rec_at))
+                rec_at += 32 + s
+            file_len[j] = rec_at - file_off[j]
+        healed = {i: np.empty(max(rec_at, 1), dtype=np.uint8) for i in targets}
+        if blocks:
+            desc = np.zeros(len(blocks), dtype=np.dtype(list(_lib.RECORD_DESC_FIELDS)))
+            desc["shard_len"] = [b[1] for b in blocks]
+            desc["rec_off"] = [b[2] for b in blocks]
+            desc["out_off"] = [b[2] for b in blocks]
+            arenas = [None if i in targets else np.empty(rec_at, dtype=np.uint8) for i in range(t)]
+            present = {}
+            for j, off in file_off.items():
+                mask = 0
+                for i, r in enumerate(raws[j]):
+                    if r is not None and arenas[i] is not None:
+                        arenas[i][off:off + len(r)] = np.frombuffer(r, dtype=np.uint8)
+                        mask |= 1 << i
+                present[j] = mask
+            desc["present"] = [present[b[0]] for b in blocks]
+            status = e.heal_mixed_host(arenas, [healed.get(i) for i in range(t)], desc, self.algo.value)
+            for i, (j, _, _) in enumerate(blocks):
+                if results[j] is not None or status[i] == _lib.RSG_OK:
+                    continue
+                if status[i] == _lib.RSG_ERR_TOO_FEW_SHARDS:
+                    results[j] = _lib.RsgError(status[i], f"heal {names[j]}: read quorum")
+                elif status[i] == _lib.RSG_ERR_INCONSISTENT_SOURCES:
+                    results[j] = _lib.InvalidDataError(status[i], f"heal {names[j]}")
+                else:
+                    results[j] = _lib.RsgError(status[i], f"heal {names[j]}")
+        for j, name in enumerate(names):
+            if results[j] is None:
+                off = file_off[j]
+                self._write_healed(name, metas[j], {i: healed[i][off:off + file_len[j]].tobytes() for i in targets})
+        if not return_exceptions:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
 
     # --------------------------------------------------------------- VERIFY
     def verify_object(self, name: str) -> List[int]:
