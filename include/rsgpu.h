@@ -513,6 +513,79 @@ int rsg_heal_mixed_host(rsg_ctx *ctx, int k, int m, size_t n, const rsg_record_d
                         const uint8_t *const *h_files, uint8_t *const *h_targets, int algo,
                         int *h_status);
 
+/* ---- mixed-length batch deep scan: verify n unrelated shard files ----
+ * The fourth mixed-length path: bitrot_verify (bitrot.rs:616-655), which
+ * LocalDisk::verify_file (local.rs:8101-8146) calls once per part per disk for
+ * the scanner's deep mode, verify_object_integrity and the heal's pre-check,
+ * over files whose part sizes, shard sizes and lengths all differ: every shard
+ * file of every object of a scan cycle in one call.  The contract is
+ * rsg_bitrot_verify_dev's, applied per file.
+ * arenas: n_arenas (1..32) byte arenas, one per disk in the intended use; a
+ * NULL arena may hold only files with file_len == 0.  File f (h_desc[f], a
+ * host array the call does not keep): file_len bytes at arenas[arena] + off,
+ * records [32-byte digest][shard_size bytes], the last one short when
+ * part_size is no multiple of shard_size.
+ * h_status[f], decided in this order:
+ *   1. RSG_ERR_FILE_SIZE_MISMATCH when want_size !=
+ *      bitrot_shard_file_size(part_size, shard_size, algo); none of the file's
+ *      bytes is read, its neighbours are unaffected;
+ *   2. RSG_ERR_BITROT_MISMATCH at the first bad digest among the records that
+ *      lie wholly inside min(file_len, want_size) (the short last record is
+ *      one of them when it is complete);
+ *   3. RSG_ERR_UNEXPECTED_EOF when file_len < want_size;
+ *   4. RSG_ERR_TRAILING_DATA when file_len > want_size;
+ *   5. RSG_OK otherwise.
+ * algo, per call: HIGHWAY256S / HIGHWAY256S_LEGACY verify the records; NONE
+ * checks sizes only and launches nothing; a whole-file algorithm is
+ * RSG_ERR_UNSUPPORTED, as in the reference.
+ * RSG_ERR_INVALID_ARG with nothing read and h_status untouched: a NULL pointer;
+ * an unknown algo; n_arenas outside 1..32; arena >= n_arenas; shard_size == 0
+ * with part_size > 0; a non-empty file in a NULL arena; a range [off,
+ * +file_len) that wraps the address space; file ranges of one arena that are
+ * not ascending and disjoint in list order (files of different arenas may
+ * interleave freely, empty files occupy nothing).  More than 2^32-1 complete
+ * records in one call (one sub-batch of the host form) is RSG_ERR_UNSUPPORTED.
+ * n == 0 is RSG_OK whatever the pointers are (the context, algo and n_arenas
+ * are still checked).  Both forms are synchronous.  No byte of any arena is
+ * written.
+ * The kernel reads whole aligned 8-byte words: up to 7 bytes on either side
+ * of a record's body may be read with it, which are bytes of the record's own
+ * header or of the 8-byte granule that holds the body's last byte.
+ *
+ * rsg_bitrot_verify_mixed_dev: device arenas; runs on `stream` and waits for
+ * it.  One launch per call whatever n is (every complete record is one entry
+ * of a table sorted by length); only a table of more than 2^20 records is cut
+ * into several launches.
+ *
+ * rsg_bitrot_verify_mixed_host: host arenas, page-locked or pageable.
+ * Consecutive files are taken into sub-batches whose per-arena spans (per
+ * arena touched: its first file's start to its last file's end), record table
+ * and flags fit RSG_MIXED_STAGE_BYTES of the host-batch staging slots; a
+ * larger file gets a sub-batch of its own.  Only what is read counts and is
+ * copied: a file's bytes past want_size, and a file without a complete record
+ * (a size mismatch, an empty part, a file cut inside its first record), are
+ * not part of a span.  A sub-batch is one H2D copy per
+ * touched arena, one table copy, one launch and one flags D2H; sub-batches
+ * overlap over the slots.
+ *
+ * Which call for a uniform part: the files of ONE part (one want_size,
+ * part_size and shard_size) go through rsg_bitrot_verify_dev, whose record
+ * walk needs no table and runs nearer to memory speed
+ * (profiles/r10/mixed_verify/); this call is for batches of files that
+ * differ. */
+typedef struct rsg_file_desc {
+    uint64_t off;        /* the file's bytes at arenas[arena] + off */
+    uint64_t file_len;   /* bytes that are there */
+    uint64_t want_size;  /* the size the caller expects (verify_file passes the file's own size) */
+    uint64_t part_size;  /* Erasure::shard_file_size(part size): body bytes of the file */
+    uint32_t shard_size; /* body bytes of a full record */
+    uint32_t arena;      /* < n_arenas */
+} rsg_file_desc;
+int rsg_bitrot_verify_mixed_dev(rsg_ctx *ctx, int algo, int n_arenas, const uint8_t *const *d_arenas,
+                                size_t n, const rsg_file_desc *h_desc, int *h_status, void *stream);
+int rsg_bitrot_verify_mixed_host(rsg_ctx *ctx, int algo, int n_arenas, const uint8_t *const *h_arenas,
+                                 size_t n, const rsg_file_desc *h_desc, int *h_status);
+
 /* Page-lock / release host memory for DMA (hipHostRegister). */
 int rsg_pin(void *ptr, size_t bytes);
 int rsg_unpin(void *ptr);

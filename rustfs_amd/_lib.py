@@ -66,6 +66,7 @@ EXPORTED = (
     "rsg_heal_records_submit", "rsg_test_fail_subbatch", "rsg_set_tuning", "rsg_get_tuning",
     "rsg_encode_mixed_dev", "rsg_encode_mixed_host", "rsg_encode_mixed_host_submit",
     "rsg_decode_mixed_dev", "rsg_decode_mixed_host", "rsg_heal_mixed_dev", "rsg_heal_mixed_host",
+    "rsg_bitrot_verify_mixed_dev", "rsg_bitrot_verify_mixed_host",
 )
 
 # Staging bytes per sub-batch of rsg_encode_mixed_host (include/rsgpu.h)
@@ -76,6 +77,10 @@ STRIPE_DESC_FIELDS = 3
 # rsg_record_desc (include/rsgpu.h): the mixed-length GET's descriptor, 24
 # bytes per stripe; RECORD_DESC_DTYPE is its numpy structured dtype
 RECORD_DESC_FIELDS = (("rec_off", "<u8"), ("out_off", "<u8"), ("shard_len", "<u4"), ("present", "<u4"))
+# rsg_file_desc (include/rsgpu.h): the mixed-length deep scan's descriptor, 40
+# bytes per shard file; np.dtype(list(FILE_DESC_FIELDS)) is its numpy dtype
+FILE_DESC_FIELDS = (("off", "<u8"), ("file_len", "<u8"), ("want_size", "<u8"), ("part_size", "<u8"),
+                    ("shard_size", "<u4"), ("arena", "<u4"))
 
 # Kernel-choice knobs (rsg_set_tuning, include/rsgpu.h) and their defaults:
 # set only through the ABI (the production library ignores RSG_* variables).
@@ -160,6 +165,8 @@ def load():
         L.rsg_decode_mixed_host.argtypes = [P, I, I, S, P, P, I, I, P, P, P]
         L.rsg_heal_mixed_dev.argtypes = [P, I, I, S, P, P, P, I, P, P]
         L.rsg_heal_mixed_host.argtypes = [P, I, I, S, P, P, P, I, P]
+        L.rsg_bitrot_verify_mixed_dev.argtypes = [P, I, I, P, S, P, P, P]
+        L.rsg_bitrot_verify_mixed_host.argtypes = [P, I, I, P, S, P, P]
         _lib = L
         return L
 

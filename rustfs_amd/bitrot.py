@@ -7,7 +7,9 @@ Mirrors:
   * ``split_and_verify`` / ``BitrotReader.read``   bitrot.rs:139-157, 227-247
   * ``bitrot_verify``                     bitrot.rs:616-655
 
-Digests are computed by librsgpu.so (rsg_hash / rsg_hash_batch_dev).
+Digests are computed by librsgpu.so (rsg_hash / rsg_hash_batch_dev); whole
+files are verified by rsg_bitrot_verify_dev (one part) and
+rsg_bitrot_verify_mixed_dev / _host (many files of different parts).
 """
 from __future__ import annotations
 
@@ -147,6 +149,77 @@ def bitrot_verify_batch(files, want_size: int, part_size: int, algo: HashAlgorit
     return _lib.status_list(status, n)
 
 
+def bitrot_verify_many(arenas, desc, algo: HashAlgorithm = HashAlgorithm.HighwayHash256S, stream=None) -> list:
+    """Mixed-length batch deep scan (rsg_bitrot_verify_mixed_dev / _host): many
+    shard files of different parts in one call.  `arenas` holds up to 32 byte
+    arenas, one per disk in the intended use: contiguous cuda uint8 tensors
+    (the device form) or C-contiguous numpy uint8 arrays (the host form), None
+    for an arena with no bytes.  `desc` lists per file [off, file_len,
+    want_size, part_size, shard_size, arena] (rsg_file_desc: a structured array
+    of _lib.FILE_DESC_FIELDS, or rows of six integers): file_len bytes at
+    arenas[arena] + off.  Returns one rsg_status per file with bitrot_verify's
+    decision order applied per file (size mismatch, first bad record, early
+    EOF, trailing data).  Every descriptor is checked against its arena before
+    anything reaches the library; a file outside its arena raises RsgError
+    with RSG_ERR_INVALID_ARG.  The files of one arena must be ascending and
+    disjoint in list order."""
+    dt = np.dtype(list(_lib.FILE_DESC_FIELDS))
+    if isinstance(desc, np.ndarray) and desc.dtype == dt:
+        d = np.ascontiguousarray(desc).reshape(-1)
+    else:
+        rows = np.asarray(desc, dtype=object).reshape(-1, len(dt.names))
+        d = np.zeros(len(rows), dtype=dt)
+        for c, name in enumerate(dt.names):
+            col = [int(v) for v in rows[:, c]]
+            if any(v < 0 or v >> (8 * dt[name].itemsize) for v in col):
+                raise _lib.RsgError(_lib.RSG_ERR_INVALID_ARG, f"mixed-length verify: {name} out of range")
+            d[name] = col
+    arenas = list(arenas)
+    if not 1 <= len(arenas) <= 32:
+        raise _lib.RsgError(_lib.RSG_ERR_INVALID_ARG, "mixed-length verify takes 1..32 arenas")
+    live = [a for a in arenas if a is not None]
+    host = all(isinstance(a, np.ndarray) for a in live)
+    dev = None
+    if host:
+        for a in live:
+            if a.dtype != np.uint8 or not a.flags.c_contiguous:
+                raise TypeError("arenas must be C-contiguous uint8 arrays")
+        sizes = [a.size if a is not None else 0 for a in arenas]
+        ptrs = [a.ctypes.data if a is not None and a.size else None for a in arenas]
+    else:
+        for a in live:
+            if isinstance(a, np.ndarray) or str(a.dtype) != "torch.uint8" or not a.is_cuda or not a.is_contiguous():
+                raise TypeError("arenas must be all numpy uint8 arrays or all contiguous cuda uint8 tensors")
+            dev = a.device
+        sizes = [a.numel() if a is not None else 0 for a in arenas]
+        ptrs = [a.data_ptr() if a is not None and a.numel() else None for a in arenas]
+    n = d.size
+    if n:
+        if int(d["arena"].max()) >= len(arenas):
+            raise _lib.RsgError(_lib.RSG_ERR_INVALID_ARG, "mixed-length verify: arena index out of range")
+        end = d["off"].astype(object) + d["file_len"].astype(object)
+        cap = np.array(sizes, dtype=object)[d["arena"]]
+        bad = np.nonzero((end > cap) & (d["file_len"] > 0))[0]
+        if bad.size:
+            raise _lib.RsgError(_lib.RSG_ERR_INVALID_ARG,
+                                f"mixed-length verify: file {int(bad[0])} outside arena {int(d['arena'][bad[0]])}")
+    status = (ctypes.c_int * max(n, 1))()
+    ap = (ctypes.c_void_p * len(arenas))(*ptrs)
+    lib = _lib.load()
+    if host:
+        code = lib.rsg_bitrot_verify_mixed_host(_lib.context(None).handle, algo.value, len(arenas), ap, n,
+                                                d.ctypes.data if n else None, status)
+    else:
+        import torch
+        if dev is None:  # nothing but empty arenas: sizes only
+            dev = torch.device("cuda", torch.cuda.current_device())
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        code = lib.rsg_bitrot_verify_mixed_dev(_lib.context(dev.index or 0).handle, algo.value, len(arenas), ap, n,
+                                               d.ctypes.data if n else None, status, s)
+    _lib.check(code, "mixed-length bitrot_verify")
+    return _lib.status_list(status, n)
+
+
 def raise_for_status(code: int) -> None:
     """bitrot_verify's error for an rsg_bitrot_verify_dev status."""
     if code == _lib.RSG_OK:
@@ -163,4 +236,4 @@ def frame_shards(shards, digests) -> list:
 
 
 __all__ = ["HashAlgorithm", "bitrot_shard_file_size", "BitrotWriter", "BitrotReader", "split_and_verify",
-           "bitrot_verify", "bitrot_verify_batch", "raise_for_status", "frame_shards", "io"]
+           "bitrot_verify", "bitrot_verify_batch", "bitrot_verify_many", "raise_for_status", "frame_shards", "io"]

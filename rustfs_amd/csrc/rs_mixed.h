@@ -1,13 +1,14 @@
 // rs_mixed.h — launchers of the mixed-length kernels: the fused encode +
 // HH256S (rs_mixed.hip) and the verify + rebuild of record stripes
-// (rs_mixed_decode.hip) and their heal (rs_mixed_heal.hip); internal to
-// librsgpu.
+// (rs_mixed_decode.hip), their heal (rs_mixed_heal.hip) and the deep scan of
+// record files (rs_mixed_verify.hip); internal to librsgpu.
 #pragma once
 
 #include "rs_kernels.h"
 #include "rs_mixed_decode_plan.h"
 #include "rs_mixed_heal_plan.h"
 #include "rs_mixed_plan.h"
+#include "rs_mixed_verify_plan.h"
 
 namespace rsg {
 
@@ -78,5 +79,18 @@ struct HealZeroParams {
     uint32_t nt;
 };
 hipError_t launch_heal_zero_headers(const HealZeroParams& p, const uint64_t* d_offs, uint64_t n, hipStream_t stream);
+
+// Kernel arguments of k_verify_mixed<DEPTH>: quad j hashes the body of unit[j]
+// (device addresses, planner order) and writes flags[unit[j].flag] = 1 where
+// the digest equals the 32 bytes in front of the body, 0 where not.
+struct VerifyMixedParams {
+    const mixed::VerifyUnit* unit;  // device table
+    uint8_t* flags;
+    uint64_t n;  // units
+    uint64_t key[4];
+};
+
+// One launch over the n units; DEPTH from Tuning::hash_depth (RSG_HASH_DEPTH).
+hipError_t launch_verify_mixed(const VerifyMixedParams& p, hipStream_t stream);
 
 }  // namespace rsg

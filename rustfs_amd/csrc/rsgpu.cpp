@@ -2862,6 +2862,219 @@ int rsg_heal_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_d
     return st;
 }
 
+}  // extern "C"
+
+// ---- mixed-length batch deep scan (rs_mixed_verify.hip, rs_mixed_verify_plan.h) ----
+
+static_assert(sizeof(rsg_file_desc) == sizeof(rsg::mixed::FileDesc) &&
+                  offsetof(rsg_file_desc, want_size) == offsetof(rsg::mixed::FileDesc, want_size) &&
+                  offsetof(rsg_file_desc, shard_size) == offsetof(rsg::mixed::FileDesc, shard_size) &&
+                  offsetof(rsg_file_desc, arena) == offsetof(rsg::mixed::FileDesc, arena),
+              "rsg_file_desc is the planner's FileDesc");
+
+namespace {
+
+// Units of one launch of the device form (a 16 MiB table): a longer sorted
+// table is cut into several launches.
+constexpr size_t kVerifyTableUnits = (size_t)1 << 20;
+
+int verify_verdict_status(rsg::mixed::VerifyVerdict v) {
+    switch (v) {
+        case rsg::mixed::kVerifyOk: return RSG_OK;
+        case rsg::mixed::kVerifySizeMismatch: return RSG_ERR_FILE_SIZE_MISMATCH;
+        case rsg::mixed::kVerifyBitrot: return RSG_ERR_BITROT_MISMATCH;
+        case rsg::mixed::kVerifyEof: return RSG_ERR_UNEXPECTED_EOF;
+        case rsg::mixed::kVerifyTrailing: return RSG_ERR_TRAILING_DATA;
+    }
+    return RSG_ERR_INVALID_ARG;
+}
+
+// Argument checks shared by the device and host forms; hs: digest bytes per
+// record of `algo`.
+int verify_mixed_check(rsg_ctx* ctx, int algo, int n_arenas, const uint8_t* const* arenas, size_t n,
+                       const rsg_file_desc* h_desc, const int* h_status, uint64_t& hs) {
+    int st = enter(ctx);
+    if (st) return st;
+    if (ctx->timing.load()) ctx->last_kernel_ms.store(-1.f);  // a call that returns early was not timed
+    if (algo < 0) return RSG_ERR_INVALID_ARG;
+    // the enum has no value for a whole-file algorithm: anything past the streaming ones is one
+    if (algo != RSG_HASH_NONE && !hash_key(algo)) return RSG_ERR_UNSUPPORTED;
+    hs = algo == RSG_HASH_NONE ? 0 : rsg::mixed::kRecHeader;
+    if (n_arenas < 1 || n_arenas > rsg::mixed::kVerifyMaxArenas) return RSG_ERR_INVALID_ARG;
+    if (n == 0) return RSG_OK;  // no pointer is looked at
+    if (!arenas || !h_desc || !h_status) return RSG_ERR_INVALID_ARG;
+    uint64_t bases[rsg::mixed::kVerifyMaxArenas] = {};
+    for (int a = 0; a < n_arenas; ++a) bases[a] = (uint64_t)(uintptr_t)arenas[a];
+    if (!rsg::mixed::validate_verify(n_arenas, n, reinterpret_cast<const rsg::mixed::FileDesc*>(h_desc), bases))
+        return RSG_ERR_INVALID_ARG;
+    return RSG_OK;
+}
+
+// The sorted table `tab` on stream s: table slices of at most `cap` units
+// through d_tab (h_tab: its page-locked source, null: copied from `tab`
+// itself, which then has to outlive the stream's work), one launch per slice,
+// flags at d_flags[unit.flag].  Nothing is waited for.
+int verify_mixed_launch(const std::vector<rsg::mixed::VerifyUnit>& tab, size_t cap, uint8_t* d_tab, uint8_t* h_tab,
+                        uint8_t* d_flags, const uint64_t* key, hipStream_t s) {
+    int st = RSG_OK;
+    for (size_t at = 0; at < tab.size() && !st; at += cap) {
+        const size_t cnt = std::min(cap, tab.size() - at), bytes = cnt * sizeof(rsg::mixed::VerifyUnit);
+        const void* src = tab.data() + at;
+        if (h_tab) {
+            // the page-locked source is free again once the previous slice's copy is done
+            if (at && (st = hip_status(hipStreamSynchronize(s)))) break;
+            std::memcpy(h_tab, src, bytes);
+            src = h_tab;
+        }
+        if ((st = hip_status(hipMemcpyAsync(d_tab, src, bytes, hipMemcpyHostToDevice, s)))) break;
+        rsg::VerifyMixedParams p;
+        p.unit = reinterpret_cast<const rsg::mixed::VerifyUnit*>(d_tab);
+        p.flags = d_flags;
+        p.n = cnt;
+        std::memcpy(p.key, key, sizeof(p.key));
+        st = hip_status(rsg::launch_verify_mixed(p, s));
+    }
+    return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsg_bitrot_verify_mixed_dev(rsg_ctx* ctx, int algo, int n_arenas, const uint8_t* const* d_arenas, size_t n,
+                                const rsg_file_desc* h_desc, int* h_status, void* stream) {
+    namespace mx = rsg::mixed;
+    uint64_t hs = 0;
+    int st = verify_mixed_check(ctx, algo, n_arenas, d_arenas, n, h_desc, h_status, hs);
+    if (st || n == 0) return st;
+    const mx::FileDesc* desc = reinterpret_cast<const mx::FileDesc*>(h_desc);
+    uint64_t bases[mx::kVerifyMaxArenas] = {};
+    for (int a = 0; a < n_arenas; ++a) bases[a] = (uint64_t)(uintptr_t)d_arenas[a];
+    std::vector<mx::VerifyUnit> units, tab;
+    std::vector<uint64_t> flag0;
+    if (!mx::expand_units(desc, 0, n, hs, bases, units, flag0)) return RSG_ERR_UNSUPPORTED;
+    std::vector<uint8_t> flags(units.size());
+    if (!units.empty()) {
+        hipStream_t s = pick_stream(ctx, stream);
+        struct Lease {  // the call's scratch, back to the pool on every return
+            rsg_ctx* ctx;
+            std::unique_ptr<RecScratch> sc;
+            ~Lease() { ctx->give_scratch(std::move(sc)); }
+        } lease{ctx, ctx->take_scratch()};
+        RecScratch& sc = *lease.sc;
+        mx::order_units_for_kernel(units, tab);
+        const size_t cap = std::min(tab.size(), kVerifyTableUnits);
+        const size_t fbytes = (size_t)mx::stage_round(tab.size()), tbytes = cap * sizeof(mx::VerifyUnit);
+        if ((st = sc.ensure(fbytes + tbytes, std::max(tbytes, tab.size())))) return st;
+        sc.tmark(s);  // the kernel-timing hook brackets the call's launches (and the table copy)
+        st = verify_mixed_launch(tab, cap, sc.d + fbytes, sc.h, sc.d, hash_key(algo), s);
+        sc.tmark(s);
+        if (!st) st = flags_to_host(sc, sc.d, flags.size(), flags.data(), s);
+        if (st) {
+            (void)hipStreamSynchronize(s);  // the scratch goes back to the pool unused
+            return st;
+        }
+        if (sc.timing) ctx->last_kernel_ms.store(sc.tsum());  // the stream was synchronised above
+    }
+    std::vector<mx::VerifyVerdict> v(n);
+    mx::reduce_verdicts(desc, 0, n, hs, flag0, flags.data(), v.data());
+    for (size_t f = 0; f < n; ++f) h_status[f] = verify_verdict_status(v[f]);
+    return RSG_OK;
+}
+
+int rsg_bitrot_verify_mixed_host(rsg_ctx* ctx, int algo, int n_arenas, const uint8_t* const* h_arenas, size_t n,
+                                 const rsg_file_desc* h_desc, int* h_status) {
+    namespace mx = rsg::mixed;
+    uint64_t hs = 0;
+    int st = verify_mixed_check(ctx, algo, n_arenas, h_arenas, n, h_desc, h_status, hs);
+    if (st || n == 0) return st;
+    const mx::FileDesc* desc = reinterpret_cast<const mx::FileDesc*>(h_desc);
+    std::vector<mx::VerifySubBatch> subs;
+    mx::split_verify(n, desc, hs, RSG_MIXED_STAGE_BYTES, subs);
+    uint64_t need = RSG_MIXED_STAGE_BYTES;  // a file larger than that grows the stage
+    for (const auto& b : subs) {
+        if (b.units > 0xffffffffull) return RSG_ERR_UNSUPPORTED;
+        need = std::max(need, mx::verify_stage_bytes(b));
+    }
+    std::vector<mx::VerifyVerdict> verdicts(n);
+    // What a slot's stream still works on: the sub-batch, its table (the
+    // source of the table copy) and the destination of its flags.
+    struct Pending {
+        const mx::VerifySubBatch* b = nullptr;
+        std::vector<mx::VerifyUnit> tab;
+        std::vector<uint64_t> flag0;
+        std::vector<uint8_t> flags;
+    } pend[rsg_ctx::kPipeSlots];
+    std::unique_lock<std::mutex> g(ctx->pipe_mu);  // held to the end: the call is synchronous
+    if (hs && (st = ctx->ensure_pipeline((size_t)need))) return st;
+    PipeRun run{ctx};
+    // wait for a slot's sub-batch and turn its flags into verdicts
+    auto finish = [&](int slot) -> int {
+        Pending& p = pend[slot];
+        if (!p.b) return RSG_OK;
+        const mx::VerifySubBatch& b = *p.b;
+        p.b = nullptr;
+        const int sy = hs ? hip_status(hipStreamSynchronize(ctx->pipe_stream[slot])) : RSG_OK;
+        if (sy) return sy;
+        mx::reduce_verdicts(desc, b.first, b.count, hs, p.flag0, p.flags.data(), verdicts.data() + b.first);
+        return RSG_OK;
+    };
+    const int fail_at = ctx->fail_subbatch.load();  // rsg_test_fail_subbatch (tests only)
+    const uint64_t* key = hash_key(algo);
+    std::vector<mx::VerifyUnit> units;
+    int sub = 0;
+    for (const auto& b : subs) {
+        const int slot = hs ? run.next_slot() : 0;
+        if ((st = finish(slot))) break;  // the slot's staging is free again
+        Pending& p = pend[slot];
+        if (sub++ == fail_at) {  // fault injection (tests only)
+            st = RSG_ERR_DEVICE;
+            break;
+        }
+        if (!hs) {  // sizes only: nothing is copied or launched
+            p.flag0.assign(b.count + 1, 0);
+            p.flags.clear();
+            p.b = &b;
+            if ((st = finish(slot))) break;
+            continue;
+        }
+        hipStream_t s = ctx->pipe_stream[slot];
+        uint8_t* at = ctx->d_stage[slot];
+        uint64_t bases[mx::kVerifyMaxArenas] = {};
+        for (int a = 0; a < n_arenas && !st; ++a) {
+            if (!(b.touched >> a & 1u)) continue;
+            const uint64_t span = b.hi[a] - b.lo[a];
+            bases[a] = (uint64_t)(uintptr_t)at - b.lo[a];
+            st = hip_status(hipMemcpyAsync(at, h_arenas[a] + b.lo[a], span, hipMemcpyHostToDevice, s));
+            at += mx::stage_round(span);
+        }
+        if (st) break;
+        if (!mx::expand_units(desc, b.first, b.count, hs, bases, units, p.flag0)) {
+            st = RSG_ERR_UNSUPPORTED;
+            break;
+        }
+        mx::order_units_for_kernel(units, p.tab);
+        p.flags.assign(units.size(), 0);
+        p.b = &b;
+        if (p.tab.empty()) continue;
+        uint8_t* d_tab = at;
+        uint8_t* d_flags = at + mx::stage_round(p.tab.size() * sizeof(mx::VerifyUnit));
+        if ((st = verify_mixed_launch(p.tab, p.tab.size(), d_tab, nullptr, d_flags, key, s))) break;
+        if ((st = hip_status(hipMemcpyAsync(p.flags.data(), d_flags, p.flags.size(), hipMemcpyDeviceToHost, s)))) break;
+    }
+    // nothing of the call is in flight when it returns, whatever its status
+    for (int slot = 0; slot < rsg_ctx::kPipeSlots; ++slot) {
+        if (st) {
+            if (run.used[slot]) (void)hipStreamSynchronize(ctx->pipe_stream[slot]);
+        } else {
+            st = finish(slot);
+        }
+    }
+    if (st) return st;
+    for (size_t f = 0; f < n; ++f) h_status[f] = verify_verdict_status(verdicts[f]);
+    return RSG_OK;
+}
+
 int rsg_set_kernel_timing(rsg_ctx* ctx, int on) {
     int st = enter(ctx);
     if (st) return st;

@@ -26,7 +26,10 @@ what exercises the codec path:
   heal_objects heals many objects at once: all their blocks, short ones
   included, are one mixed-length batch (rsg_heal_mixed_host).
 * VERIFY: deep-scan every shard file (bitrot_verify, bitrot.rs:616-655) with
-  one rsg_bitrot_verify_dev call.
+  one rsg_bitrot_verify_dev call.  verify_objects scans many objects at once:
+  every shard file of every object is one file of one mixed-length batch
+  (rsg_bitrot_verify_mixed_host), the fourth side of put_objects, get_objects
+  and heal_objects.
 
 Commit: a PUT writes every shard file into a directory of its own version id
 (the reference's per-version data_dir, which xl.meta points to), and only once
@@ -644,3 +647,57 @@ class LocalErasureSet:
         status = bitrot_verify_batch(present, want, part, self.algo, S) if present else []
         it = iter(status)
         return [_lib.RSG_ERR_UNEXPECTED_EOF if f is None else next(it) for f in files]
+
+    def verify_objects(self, names: Sequence[str], return_exceptions: bool = False) -> list:
+        """Deep scan of many objects with one call, the fourth side of
+        put_objects, get_objects and heal_objects: every shard file of every
+        object is one file of one mixed-length batch
+        (rsg_bitrot_verify_mixed_host), each disk's files packed into that
+        disk's host arena.  Entry j equals verify_object(names[j]): the
+        rsg_status of every shard file, a file that cannot be opened being
+        RSG_ERR_UNEXPECTED_EOF (it gets no descriptor).  An object without
+        readable metadata yields the exception verify_object would have raised,
+        in its place with return_exceptions; otherwise the first one is raised.
+        Memory: every shard file of every name is held at once, as read and
+        again in its disk's arena (about twice the files' total bytes at the
+        peak), so a caller scanning a large set passes the names in slices of
+        the size it can afford; each slice is one call."""
+        from .bitrot import bitrot_verify_many
+        e, t = self.erasure, self.k + self.m
+        S = e.shard_size()
+        results: list = [None] * len(names)
+        raws: List[list] = [[] for _ in range(t)]  # per disk: the files' bytes, in list order
+        at = [0] * t
+        rows = []   # (off, file_len, want_size, part_size, shard_size, arena)
+        where = []  # (object, disk) of each row
+        for j, name in enumerate(names):
+            try:
+                meta = self._meta(name)
+            except Exception as ex:  # no metadata, no read quorum on it
+                results[j] = ex
+                continue
+            part = e.shard_file_size(meta["size"])
+            want = bitrot_shard_file_size(part, S, self.algo)
+            results[j] = [_lib.RSG_ERR_UNEXPECTED_EOF] * t
+            for i in range(t):
+                try:
+                    with open(self._path(i, name, meta["version"]), "rb") as f:
+                        raw = f.read()
+                except OSError:
+                    continue
+                rows.append((at[i], len(raw), want, part, S, i))
+                where.append((j, i))
+                if raw:
+                    raws[i].append(raw)
+                    at[i] += len(raw)
+        if rows:
+            arenas = [np.frombuffer(b"".join(r), dtype=np.uint8) if r else None for r in raws]
+            desc = np.array(rows, dtype=np.dtype(list(_lib.FILE_DESC_FIELDS)))
+            status = bitrot_verify_many(arenas, desc, self.algo)
+            for (j, i), st in zip(where, status):
+                results[j][i] = st
+        if not return_exceptions:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
