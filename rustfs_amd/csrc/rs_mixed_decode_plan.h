@@ -4,11 +4,17 @@
 // its own set of present shards.  Plain C++17, no HIP headers: it compiles and
 // runs on a CPU (tests/host/mixed_decode_plan_main.cpp).
 //
-// The planner validates the caller's descriptors, groups the stripes of a
-// launch by their mask of readable shards (one decode plan and one launch per
-// distinct mask), orders each group for the kernel, splits a host batch into
-// sub-batches that fit the staging buffers, and, from the verify flags of a
-// finished round, finds the stripes to run again under a smaller mask.
+// The planner validates the caller's descriptors, splits a host batch into
+// sub-batches that fit the staging buffers, and plans the rounds of a launch
+// sequence: a round groups the stripes still to do by their mask of readable
+// shards (one plan and one launch per distinct mask), orders each group for
+// the kernel into one concatenated table, and, from the verify flags the
+// launches leave, finds the stripes to run again under a smaller mask.
+//
+// Everything from OutRule down is the record-stripe machinery the mixed-length
+// heal (rs_mixed_heal_plan.h) runs through as well: the two operations differ
+// in their validation, in the plan of a mask (plan_mask here, plan_heal_mask
+// there) and in the out range of a stripe (get_out_rule, heal_out_rule).
 #pragma once
 
 #include <stddef.h>
@@ -108,36 +114,53 @@ inline bool validate_decode(int k, int m, size_t n, const RecordDesc* d, const u
     return true;
 }
 
-// The decode plan of one mask: the first k readable shards in ascending index
-// are the sources (the oracle's rule), the data shards outside the mask are
-// rebuilt, and, when something is rebuilt and `verify_surplus`, every readable
-// shard past the sources is re-derived and compared.  When every data shard
-// is readable nothing is rebuilt and no parity record is read.  False: fewer
-// than k readable shards.
+// The plan of one mask, for GET and heal alike: the sources, the computed rows
+// that are written (GET: the lost data shards; heal: the targets; never read),
+// and the surplus shards, which are read, re-derived and compared.
 struct MaskPlan {
-    std::vector<int> src, lost, surplus;
+    std::vector<int> src, written, surplus;
     uint32_t read_mask() const {
         uint32_t r = 0;
         for (int i : src) r |= 1u << i;
         for (int i : surplus) r |= 1u << i;
         return r;
     }
+    int rows() const { return (int)(written.size() + surplus.size()); }  // computed rows
 };
 
+// The decode plan of one mask: the first k readable shards in ascending index
+// are the sources (the oracle's rule), the data shards outside the mask are
+// rebuilt, and, when something is rebuilt and `verify_surplus`, every readable
+// shard past the sources is re-derived and compared.  When every data shard
+// is readable nothing is rebuilt and no parity record is read.  False: fewer
+// than k readable shards.
 inline bool plan_mask(int k, int m, uint32_t mask, bool verify_surplus, MaskPlan& p) {
     p.src.clear();
-    p.lost.clear();
+    p.written.clear();
     p.surplus.clear();
     if (popcount32(mask) < k) return false;
     for (int i = 0; i < k; ++i)
-        if (!(mask >> i & 1u)) p.lost.push_back(i);
+        if (!(mask >> i & 1u)) p.written.push_back(i);
     for (int i = 0; i < k + m; ++i) {
         if (!(mask >> i & 1u)) continue;
         if ((int)p.src.size() < k) p.src.push_back(i);
-        else if (verify_surplus && !p.lost.empty()) p.surplus.push_back(i);
+        else if (verify_surplus && !p.written.empty()) p.surplus.push_back(i);
     }
     return true;
 }
+
+// The out-range rule of an operation: a stripe of shard length len occupies
+// [out_off, +bytes(len)) of every one of the `copies` out arenas, and nothing,
+// its out_off not looked at, where bytes(len) is 0.
+struct OutRule {
+    uint64_t fixed, per_byte;
+    int copies;
+    constexpr uint64_t bytes(uint32_t len) const { return fixed + per_byte * len; }
+};
+
+// GET: the k rebuilt data shards side by side in the one out arena; an empty
+// stripe occupies nothing.
+constexpr OutRule get_out_rule(int k) { return OutRule{0, (uint64_t)k, 1}; }
 
 // Stripes that share a mask, in the order given (stable: caller order holds
 // inside a group); groups in order of first appearance.
@@ -159,87 +182,141 @@ inline void group_by_mask(const uint32_t* masks, const std::vector<uint32_t>& to
     }
 }
 
-// The kernel's table for one group: sorted by chunk count, descending (stable:
-// equal counts keep the group's order), offsets relative to (rec_lo, out_lo),
-// job = stripe index - first (the launch's flag arrays are in caller order
-// whatever the table's order).  A zero-length stripe gets out_off 0.
-inline void order_group_for_kernel(const RecordDesc* d, const std::vector<uint32_t>& stripes, size_t first,
-                                   uint64_t rec_lo, uint64_t out_lo, std::vector<DecDesc>& out) {
-    out.resize(stripes.size());
-    for (size_t i = 0; i < stripes.size(); ++i) {
-        const RecordDesc& s = d[stripes[i]];
-        DecDesc& o = out[i];
-        o.len = s.shard_len;
-        o.job = (uint32_t)(stripes[i] - first);
-        o.rec_off = s.rec_off - rec_lo;
-        o.out_off = s.shard_len ? s.out_off - out_lo : 0;
+// The kernel's table for one group, appended to `out`: sorted by chunk count,
+// descending (stable: equal counts keep the group's order), offsets relative
+// to (rec_lo, out_lo), job = stripe index - first (the launch's flag arrays
+// are in caller order whatever the table's order).  A stripe without an out
+// range gets out_off 0.
+inline void order_group_for_kernel(const OutRule& rule, const RecordDesc* d, const std::vector<uint32_t>& stripes,
+                                   size_t first, uint64_t rec_lo, uint64_t out_lo, std::vector<DecDesc>& out) {
+    const size_t at = out.size();
+    out.reserve(at + stripes.size());
+    for (uint32_t j : stripes) {
+        const RecordDesc& s = d[j];
+        out.push_back(DecDesc{s.rec_off - rec_lo, rule.bytes(s.shard_len) ? s.out_off - out_lo : 0, s.shard_len,
+                              (uint32_t)(j - first)});
     }
-    std::stable_sort(out.begin(), out.end(),
+    std::stable_sort(out.begin() + (ptrdiff_t)at, out.end(),
                      [](const DecDesc& a, const DecDesc& b) { return chunks_of(a.len) > chunks_of(b.len); });
 }
 
-// A run of consecutive caller-order stripes handled as one unit by the host
-// form: the record span [rec_lo, rec_hi) of every arena goes up, the out span
-// [out_lo, out_hi) is staged beside it (out_lo = out_hi = 0 without a
-// non-empty stripe).
-struct DecSubBatch {
+// A run of consecutive caller-order stripes handled as one unit by a host
+// form: the record span [rec_lo, rec_hi) of every arena that may be read goes
+// up, the out span [out_lo, out_hi) is staged beside it once per out arena
+// (out_lo = out_hi = 0 without a stripe that has an out range).
+struct RecSubBatch {
     size_t first, count;
     uint64_t rec_lo, rec_hi, out_lo, out_hi;
 };
 
 // Staging bytes of a sub-batch: the record span once per arena copied up, the
-// out span (each region 256-byte aligned).
-inline uint64_t decode_stage_bytes(const DecSubBatch& b, int files) {
-    return (uint64_t)files * stage_round(b.rec_hi - b.rec_lo) + stage_round(b.out_hi - b.out_lo);
+// out span once per out arena (each region 256-byte aligned).
+inline uint64_t record_stage_bytes(const OutRule& rule, const RecSubBatch& b, int files) {
+    return (uint64_t)files * stage_round(b.rec_hi - b.rec_lo) + (uint64_t)rule.copies * stage_round(b.out_hi - b.out_lo);
 }
 
 // Split a validated list into sub-batches of at most `stage` staging bytes
 // (and `max_count` stripes) with `files` arenas copied up.  A single stripe
 // larger than `stage` gets a sub-batch of its own.  Covers every stripe once,
 // in order.
-inline void split_decode(int k, int files, size_t n, const RecordDesc* d, uint64_t stage, size_t max_count,
-                         std::vector<DecSubBatch>& out) {
+inline void split_records(const OutRule& rule, int files, size_t n, const RecordDesc* d, uint64_t stage,
+                          size_t max_count, std::vector<RecSubBatch>& out) {
     out.clear();
     size_t i = 0;
     while (i < n) {
-        DecSubBatch b{i, 0, 0, 0, 0, 0};
+        RecSubBatch b{i, 0, 0, 0, 0, 0};
         bool have_out = false;
         while (i < n && b.count < max_count) {
-            DecSubBatch t = b;
+            RecSubBatch t = b;
             t.count = b.count + 1;
-            const uint64_t len = d[i].shard_len;
+            const uint64_t ol = rule.bytes(d[i].shard_len);
             if (b.count == 0) t.rec_lo = d[i].rec_off;
-            t.rec_hi = d[i].rec_off + kRecHeader + len;
-            if (len) {
+            t.rec_hi = d[i].rec_off + kRecHeader + d[i].shard_len;
+            if (ol) {
                 if (!have_out) t.out_lo = d[i].out_off;
-                t.out_hi = d[i].out_off + (uint64_t)k * len;
+                t.out_hi = d[i].out_off + ol;
             }
-            if (b.count && decode_stage_bytes(t, files) > stage) break;
+            if (b.count && record_stage_bytes(rule, t, files) > stage) break;
             b = t;
-            have_out = have_out || len != 0;
+            have_out = have_out || ol != 0;
             ++i;
         }
         out.push_back(b);
     }
 }
 
+// One round over the stripes of `todo`: their groups by mask; for every group
+// whose mask has a plan, a launch; the launches' tables, concatenated in launch
+// order.  A group without a plan (too few readable shards) has no launch and
+// read[] 0: nothing of it is read.
+struct RoundLaunch {
+    size_t group;                // index into groups
+    size_t at, n;                // its slice of the table
+    MaskPlan plan;
+    std::vector<int> row_shard;  // kernel row -> shard read for it; -1: a written row, not read
+};
+
+struct Round {
+    std::vector<MaskGroup> groups;
+    std::vector<uint32_t> read;  // per group: the shards its launch reads, 0 without a launch
+    std::vector<RoundLaunch> launches;
+    std::vector<DecDesc> table;
+};
+
+// plan(mask, MaskPlan&) is the operation's plan of a mask (plan_mask,
+// plan_heal_mask); rows are the sources, then the written, then the surplus.
+template <class PlanFn>
+inline void plan_round(const OutRule& rule, const RecordDesc* d, size_t first, uint64_t rec_lo, uint64_t out_lo,
+                       const uint32_t* masks, const std::vector<uint32_t>& todo, PlanFn plan, Round& r) {
+    group_by_mask(masks, todo, r.groups);
+    r.read.assign(r.groups.size(), 0);
+    r.launches.clear();
+    r.table.clear();
+    MaskPlan p;
+    for (size_t g = 0; g < r.groups.size(); ++g) {
+        if (!plan(r.groups[g].mask, p)) continue;
+        r.read[g] = p.read_mask();
+        const size_t at = r.table.size();
+        order_group_for_kernel(rule, d, r.groups[g].stripes, first, rec_lo, out_lo, r.table);
+        r.launches.push_back(RoundLaunch{g, at, r.table.size() - at, p, p.src});
+        std::vector<int>& rs = r.launches.back().row_shard;
+        rs.insert(rs.end(), p.written.size(), -1);
+        rs.insert(rs.end(), p.surplus.begin(), p.surplus.end());
+    }
+}
+
+// After the launches of a round: the kernels' flags, rows[job*fstride + row]
+// (job = stripe - first), to flags by shard, flags[(s - first)*fstride + shard],
+// for every stripe of every launch and every row read.  Other entries of
+// `flags` stay as they are.
+inline void shard_flags_from_rows(const Round& r, size_t first, const uint8_t* rows, size_t fstride, uint8_t* flags) {
+    for (const RoundLaunch& l : r.launches) {
+        const int* row_shard = l.row_shard.data();
+        const size_t nrows = l.row_shard.size();
+        for (uint32_t s : r.groups[l.group].stripes) {  // the stripes of the launch's slice, in caller order
+            const uint8_t* in = rows + (s - first) * fstride;
+            uint8_t* out = flags + (s - first) * fstride;
+            for (size_t row = 0; row < nrows; ++row)
+                if (row_shard[row] >= 0) out[row_shard[row]] = in[row];
+        }
+    }
+}
+
 // After a round: flags[(s - first)*fstride + i] is 1 where shard i's record of
 // stripe s verified, 0 where it did not, and is looked at only for the shards
-// the stripe's plan read.  Every stripe of `groups` whose verified set is
-// smaller than its mask gets the unverified bits cleared in masks[s] and goes
-// into `redo` (ascending).  Each redone stripe loses at least one bit, so a
-// stripe is redone at most k+m times.
-inline void redo_from_flags(int k, int m, bool verify_surplus, const std::vector<MaskGroup>& groups, size_t first,
+// of read[g], the shards the launch of the stripe's group read (0: no launch).
+// Every stripe whose verified set is smaller than its mask gets the unverified
+// bits cleared in masks[s] and goes into `redo` (ascending).  Each redone
+// stripe loses at least one bit, so a stripe is redone at most t = k+m times.
+inline void redo_from_flags(int t, const std::vector<MaskGroup>& groups, const uint32_t* read, size_t first,
                             const uint8_t* flags, size_t fstride, uint32_t* masks, std::vector<uint32_t>& redo) {
     redo.clear();
-    MaskPlan p;
-    for (const MaskGroup& g : groups) {
-        if (!plan_mask(k, m, g.mask, verify_surplus, p)) continue;  // no launch: nothing was read
-        const uint32_t read = p.read_mask();
-        for (uint32_t s : g.stripes) {
+    for (size_t g = 0; g < groups.size(); ++g) {
+        if (!read[g]) continue;
+        for (uint32_t s : groups[g].stripes) {
             uint32_t bad = 0;
-            for (int i = 0; i < k + m; ++i)
-                if ((read >> i & 1u) && !flags[(s - first) * fstride + (size_t)i]) bad |= 1u << i;
+            for (int i = 0; i < t; ++i)
+                if ((read[g] >> i & 1u) && !flags[(s - first) * fstride + (size_t)i]) bad |= 1u << i;
             if (bad) {
                 masks[s] &= ~bad;
                 redo.push_back(s);

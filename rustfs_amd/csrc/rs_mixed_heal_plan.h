@@ -7,10 +7,15 @@
 //
 // Shared with the mixed-length GET (rs_mixed_decode_plan.h): the descriptors
 // (RecordDesc, whose out_off here is the offset of the stripe's record in every
-// target arena; DecDesc), grouping by mask, the kernel order by descending
-// chunk count with `job` mapping back, and the redo rule.  Heal-specific: the
-// validation of target ranges, the plan of a mask (targets are computed and
-// never read) and the sub-batches of the host form.
+// target arena; DecDesc), the plan struct (MaskPlan: the targets are its
+// written rows), the sub-batches of the host form (split_records,
+// record_stage_bytes), and the whole of a round: grouping by mask, the kernel
+// order by descending chunk count with `job` mapping back, the concatenated
+// table and row_shard[] of every launch (plan_round), the kernel's row flags
+// to shard flags (shard_flags_from_rows) and the redo rule (redo_from_flags).
+// Heal-specific, all of it here: the kernel's shapes, the validation of target
+// ranges, the plan of a mask (plan_heal_mask: targets are computed and never
+// read) and the out-range rule (heal_out_rule: the record, empty stripes too).
 #pragma once
 
 #include "rs_mixed_decode_plan.h"
@@ -88,30 +93,19 @@ inline bool validate_heal(int k, int m, size_t n, const RecordDesc* d, const uin
 
 // The heal plan of one mask of readable non-target shards: the first k of them
 // in ascending index are the sources (the oracle's rule); the computed rows
-// are all targets, then every readable shard past the sources, which is
-// re-derived and compared (heal.rs:180-196).  The surplus shards are parity
+// are all targets (written), then every readable shard past the sources, which
+// is re-derived and compared (heal.rs:180-196).  The surplus shards are parity
 // shards: the sources take the first k readable ones and there are k data
-// shards.  R = targets + surplus <= m whenever the plan exists.  False: fewer
-// than k readable shards (more than m targets always ends here).
-struct HealPlan {
-    std::vector<int> src, tgt, surplus;
-    uint32_t read_mask() const {
-        uint32_t r = 0;
-        for (int i : src) r |= 1u << i;
-        for (int i : surplus) r |= 1u << i;
-        return r;
-    }
-    int rows() const { return (int)(tgt.size() + surplus.size()); }
-};
-
-inline bool plan_heal_mask(int k, int m, uint32_t mask, uint32_t targets, HealPlan& p) {
+// shards.  rows() <= m whenever the plan exists.  False: fewer than k readable
+// shards (more than m targets always ends here).
+inline bool plan_heal_mask(int k, int m, uint32_t mask, uint32_t targets, MaskPlan& p) {
     p.src.clear();
-    p.tgt.clear();
+    p.written.clear();
     p.surplus.clear();
     mask &= ~targets;
     if (popcount32(mask) < k) return false;
     for (int i = 0; i < k + m; ++i) {
-        if (targets >> i & 1u) p.tgt.push_back(i);
+        if (targets >> i & 1u) p.written.push_back(i);
         if (!(mask >> i & 1u)) continue;
         if ((int)p.src.size() < k) p.src.push_back(i);
         else p.surplus.push_back(i);
@@ -119,81 +113,9 @@ inline bool plan_heal_mask(int k, int m, uint32_t mask, uint32_t targets, HealPl
     return true;
 }
 
-// The kernel's table for one group: order_group_for_kernel's order and `job`,
-// with out_off the record's offset in the target arenas relative to out_lo,
-// for zero-length stripes too (their record is the bare digest).
-inline void order_heal_group_for_kernel(const RecordDesc* d, const std::vector<uint32_t>& stripes, size_t first,
-                                        uint64_t rec_lo, uint64_t out_lo, std::vector<DecDesc>& out) {
-    order_group_for_kernel(d, stripes, first, rec_lo, out_lo, out);
-    for (DecDesc& o : out) o.out_off = d[first + o.job].out_off - out_lo;
-}
-
-// A run of consecutive caller-order stripes handled as one unit by the host
-// form: the record span [rec_lo, rec_hi) of every arena that may be read goes
-// up, the target span [out_lo, out_hi) is staged once per target and comes
-// back whole.
-struct HealSubBatch {
-    size_t first, count;
-    uint64_t rec_lo, rec_hi, out_lo, out_hi;
-};
-
-// Staging bytes of a sub-batch: the record span once per arena copied up, the
-// target span once per target (each region 256-byte aligned).
-inline uint64_t heal_stage_bytes(const HealSubBatch& b, int files, int targets) {
-    return (uint64_t)files * stage_round(b.rec_hi - b.rec_lo) + (uint64_t)targets * stage_round(b.out_hi - b.out_lo);
-}
-
-// Split a validated list into sub-batches of at most `stage` staging bytes
-// (and `max_count` stripes) with `files` arenas copied up and `targets`
-// targets staged.  A single stripe larger than `stage` gets a sub-batch of its
-// own.  Covers every stripe once, in order.
-inline void split_heal(int files, int targets, size_t n, const RecordDesc* d, uint64_t stage, size_t max_count,
-                       std::vector<HealSubBatch>& out) {
-    out.clear();
-    size_t i = 0;
-    while (i < n) {
-        HealSubBatch b{i, 0, 0, 0, 0, 0};
-        while (i < n && b.count < max_count) {
-            HealSubBatch t = b;
-            t.count = b.count + 1;
-            const uint64_t rl = kRecHeader + d[i].shard_len;
-            if (b.count == 0) {
-                t.rec_lo = d[i].rec_off;
-                t.out_lo = d[i].out_off;
-            }
-            t.rec_hi = d[i].rec_off + rl;
-            t.out_hi = d[i].out_off + rl;
-            if (b.count && heal_stage_bytes(t, files, targets) > stage) break;
-            b = t;
-            ++i;
-        }
-        out.push_back(b);
-    }
-}
-
-// redo_from_flags for heal plans: every stripe of `groups` in which a record
-// its plan read did not verify loses those bits in masks[s] and goes into
-// `redo` (ascending).  Each redone stripe loses at least one bit, so a stripe
-// is redone at most k+m times.
-inline void redo_heal_from_flags(int k, int m, uint32_t targets, const std::vector<MaskGroup>& groups, size_t first,
-                                 const uint8_t* flags, size_t fstride, uint32_t* masks, std::vector<uint32_t>& redo) {
-    redo.clear();
-    HealPlan p;
-    for (const MaskGroup& g : groups) {
-        if (!plan_heal_mask(k, m, g.mask, targets, p)) continue;  // no launch: nothing was read
-        const uint32_t read = p.read_mask();
-        for (uint32_t s : g.stripes) {
-            uint32_t bad = 0;
-            for (int i = 0; i < k + m; ++i)
-                if ((read >> i & 1u) && !flags[(s - first) * fstride + (size_t)i]) bad |= 1u << i;
-            if (bad) {
-                masks[s] &= ~bad;
-                redo.push_back(s);
-            }
-        }
-    }
-    std::sort(redo.begin(), redo.end());
-}
+// Heal: the stripe's record [digest][shard] in every one of the `targets`
+// target arenas; an empty stripe's record is the bare digest.
+constexpr OutRule heal_out_rule(int targets) { return OutRule{kRecHeader, 1, targets}; }
 
 }  // namespace mixed
 }  // namespace rsg

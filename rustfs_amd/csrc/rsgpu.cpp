@@ -2273,7 +2273,7 @@ int rsg_encode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_stripe
 
 }  // extern "C"
 
-// ---- mixed-length batch GET (rs_mixed_decode.hip, rs_mixed_decode_plan.h) ----
+// ---- record-stripe rounds: the host engine of the mixed-length GET and heal ----
 
 namespace {
 
@@ -2282,46 +2282,168 @@ static_assert(sizeof(rsg_record_desc) == sizeof(rsg::mixed::RecordDesc) &&
                   offsetof(rsg_record_desc, present) == offsetof(rsg::mixed::RecordDesc, present),
               "rsg_record_desc is the planner's RecordDesc");
 
-// The kernel's arguments for one mask group: sources, lost rows, surplus rows
-// and their coefficient rows (plan_row over the codec's DecodePlan).
-int decode_mixed_params(Codec* cd, int k, int m, uint32_t mask, const rsg::mixed::MaskPlan& mp,
-                        const uint8_t* const* d_files, uint8_t* d_out, const uint64_t* key, uint8_t* d_flags,
-                        uint32_t* d_mismatch, rsg::DecodeMixedParams& p, int* row_shard) {
-    std::memset(&p, 0, sizeof(p));
-    const int e = (int)mp.lost.size(), R = e + (int)mp.surplus.size();
-    if (R > rsg::mixed::kDecMaxR) return RSG_ERR_UNSUPPORTED;
+// The arguments every record-stripe kernel takes (DecodeMixedParams,
+// HealMixedParams) for the launch of one plan: the shape, the flag arrays, the
+// key, the arenas of the rows read, and the computed rows' coefficient rows
+// (plan_row over the codec's DecodePlan of `mask`).  The operation's own
+// fields are its caller's.
+template <class Params>
+int record_params(Codec* cd, int k, int m, uint32_t mask, const rsg::mixed::MaskPlan& mp,
+                  const uint8_t* const* d_files, const uint64_t* key, uint8_t* d_flags, uint32_t* d_mismatch,
+                  Params& p) {
+    const int e = (int)mp.written.size(), R = mp.rows();
     p.C = (uint32_t)k;
     p.R = (uint32_t)R;
     p.e = (uint32_t)e;
     p.fstride = (uint32_t)(k + m);
-    p.out = d_out;
     p.flags = d_flags;
     p.mismatch = d_mismatch;
     std::memcpy(p.key, key, sizeof(p.key));
-    for (int c = 0; c < k; ++c) {
-        p.file[c] = d_files[mp.src[c]];
-        row_shard[c] = mp.src[c];
-    }
-    for (int r = 0; r < R; ++r) row_shard[k + r] = -1;
-    if (R == 0) return RSG_OK;
+    for (int c = 0; c < k; ++c) p.file[c] = d_files[mp.src[c]];
+    if (R == 0) return RSG_OK;  // nothing computed: no coefficients, no codec (m = 0)
     std::vector<uint8_t> present((size_t)(k + m), 0);
     for (int i = 0; i < k + m; ++i) present[i] = (mask >> i & 1u) ? 1 : 0;
     std::shared_ptr<DecodePlan> plan = cd->plan(present.data());
     if (!plan) return RSG_ERR_TOO_FEW_SHARDS;
     std::vector<uint8_t> row((size_t)k);
     for (int r = 0; r < R; ++r) {
-        const int shard = r < e ? mp.lost[r] : mp.surplus[r - e];
-        if (r < e) {
-            p.lost[r] = (uint32_t)shard;
-        } else {
-            p.file[k + r] = d_files[shard];
-            row_shard[k + r] = shard;
-        }
+        const int shard = r < e ? mp.written[r] : mp.surplus[r - e];
+        if (r >= e) p.file[k + r] = d_files[shard];
         plan_row(*cd, *plan, shard, row.data());
         for (int c = 0; c < k; ++c) coef_tables(row[c], p.tab[r][c]);
     }
     return RSG_OK;
 }
+
+// The rounds of a record-stripe operation over stripes d[0 .. count) of a
+// validated list on stream s, to the end (the stream is waited for): shard i's
+// record of stripe j at d_files[i] + d[j].rec_off - rec_lo, its out range
+// (`rule`) at d[j].out_off - out_lo of the operation's out arenas.  masks[j]:
+// the shards stripe j may read; on return, those it ended with (every one it
+// read verified, or fewer than k left).
+//
+// A round plans the stripes still to do (rs_mixed_decode_plan.h: one launch
+// per mask that has a plan), uploads the launches' tables in one copy, launches,
+// fetches [flags][mismatch] in one copy, waits, and redoes the stripes in which
+// a record read did not verify under their smaller mask.
+//
+// The operation supplies: plan(mask, MaskPlan&), its plan of a mask;
+// own(plan, Params&), its check of the plan's shape and its own argument
+// fields (nonzero: the call's status); `launch`, its kernel's launcher; `extra`
+// scratch bytes of its own between [flags][mismatch] and the table; and
+// end(h_mismatch, d_extra, h_extra), run after the last round while the scratch
+// is still the call's (h_mismatch[j] nonzero: a surplus row of stripe j
+// differed; work it queues on s is waited for by it).
+template <class Params, class PlanFn, class OwnFn, class EndFn>
+int record_rounds(rsg_ctx* ctx, Codec* cd, int k, int m, const rsg::mixed::OutRule& rule,
+                  const rsg::mixed::RecordDesc* d, size_t count, uint64_t rec_lo, uint64_t out_lo,
+                  const uint8_t* const* d_files, const uint64_t* key, size_t extra, uint32_t* masks, PlanFn plan,
+                  OwnFn own,
+                  hipError_t (*launch)(const Params&, const rsg::mixed::DecDesc*, uint64_t, hipStream_t), EndFn end,
+                  hipStream_t s) {
+    namespace mx = rsg::mixed;
+    const size_t T = (size_t)(k + m);
+    // scratch: [flags][mismatch][extra][table]
+    const size_t fbytes = (size_t)mx::stage_round((uint64_t)count * T);
+    const size_t mbytes = (size_t)mx::stage_round((uint64_t)count * 4);
+    const size_t tbytes = count * sizeof(mx::DecDesc);
+    std::unique_ptr<rsg_ctx::MixedTab> mt = ctx->take_mixed_tab();
+    if (!mt) return RSG_ERR_DEVICE;
+    int st = mt->buf.ensure(fbytes + mbytes + extra + tbytes, fbytes + mbytes + extra + tbytes);
+    if (st) return st;
+    uint8_t* d_flags = mt->buf.d;
+    uint32_t* d_mis = (uint32_t*)(mt->buf.d + fbytes);
+    const mx::DecDesc* d_tab = (const mx::DecDesc*)(mt->buf.d + fbytes + mbytes + extra);
+    uint8_t* h_tab = mt->buf.h + fbytes + mbytes + extra;
+    st = hip_status(hipMemsetAsync(d_mis, 0, mbytes, s));
+
+    std::vector<uint32_t> todo(count), redo;
+    for (size_t j = 0; j < count; ++j) todo[j] = (uint32_t)j;
+    std::vector<uint8_t> flags(count * T, 1);  // by shard
+    mx::Round round;
+    std::vector<Params> params;
+    while (!st && !todo.empty()) {
+        mx::plan_round(rule, d, 0, rec_lo, out_lo, masks, todo, plan, round);
+        params.resize(round.launches.size());
+        for (size_t i = 0; i < params.size() && !st; ++i) {
+            const mx::RoundLaunch& l = round.launches[i];
+            std::memset(&params[i], 0, sizeof(Params));
+            if ((st = own(l.plan, params[i]))) break;
+            st = record_params(cd, k, m, round.groups[l.group].mask, l.plan, d_files, key, d_flags, d_mis, params[i]);
+        }
+        if (st || params.empty()) break;  // no launch: only stripes with too few shards are left
+        const size_t tab_bytes = round.table.size() * sizeof(mx::DecDesc);
+        std::memcpy(h_tab, round.table.data(), tab_bytes);
+        st = hip_status(hipMemcpyAsync((void*)d_tab, h_tab, tab_bytes, hipMemcpyHostToDevice, s));
+        for (size_t i = 0; i < params.size() && !st; ++i)
+            st = hip_status(launch(params[i], d_tab + round.launches[i].at, round.launches[i].n, s));
+        if (!st) st = hip_status(hipMemcpyAsync(mt->buf.h, mt->buf.d, fbytes + mbytes, hipMemcpyDeviceToHost, s));
+        if (!st) st = hip_status(hipStreamSynchronize(s));
+        if (st) break;
+        mx::shard_flags_from_rows(round, 0, mt->buf.h, T, flags.data());
+        mx::redo_from_flags((int)T, round.groups, round.read.data(), 0, flags.data(), T, masks, redo);
+        todo.swap(redo);
+    }
+    if (!st)
+        st = end((const uint32_t*)(mt->buf.h + fbytes), mt->buf.d + fbytes + mbytes, mt->buf.h + fbytes + mbytes);
+    if (st) (void)hipStreamSynchronize(s);
+    ctx->give_mixed_tab(std::move(mt), s);
+    return st;
+}
+
+// Staging of the host form of a record-stripe operation.  The kernel's
+// geometries stage through the host-batch slots (pipe_mu held to the end: the
+// call is synchronous).  The per-length engine keeps its own tickets under
+// pipe_mu, so the other geometries stage through a buffer of the call's own on
+// the null stream.
+struct RecordStaging {
+    rsg_ctx* ctx;
+    const bool slots;
+    std::unique_lock<std::mutex> g;
+    struct Own {
+        uint8_t* d = nullptr;
+        ~Own() {
+            if (d) (void)hipFree(d);
+        }
+    } own;
+    PipeRun run;
+    hipStream_t s = nullptr;   // of the current sub-batch
+    uint8_t* stage = nullptr;  // likewise
+
+    RecordStaging(rsg_ctx* c, bool kernel_geometry)
+        : ctx(c), slots(kernel_geometry), g(c->pipe_mu, std::defer_lock), run{c} {}
+    int open(size_t need) {
+        if (!slots) return hip_status(hipMalloc((void**)&own.d, need));
+        g.lock();
+        return ctx->ensure_pipeline(need);
+    }
+    void next_sub_batch() {
+        const int slot = slots ? run.next_slot() : 0;
+        s = slots ? ctx->pipe_stream[slot] : nullptr;
+        stage = slots ? ctx->d_stage[slot] : own.d;
+    }
+};
+
+// Up, into consecutive stage_round(rspan) regions from `stage`: the record span
+// [rec_lo, +rspan) of every arena that is there, is not in `never_read`, and
+// that some stripe of d[0 .. count) may read; dfiles[i]: arena i's copy.
+int upload_may_read(int T, const rsg::mixed::RecordDesc* d, size_t count, const uint8_t* const* h_files,
+                    uint32_t never_read, uint64_t rec_lo, uint64_t rspan, uint8_t* stage, hipStream_t s,
+                    const uint8_t** dfiles) {
+    uint32_t may = 0;
+    for (size_t j = 0; j < count; ++j) may |= d[j].present;
+    may &= ~never_read;
+    int st = RSG_OK;
+    for (int i = 0; i < T && !st; ++i) {
+        if (!h_files[i] || !(may >> i & 1u)) continue;
+        dfiles[i] = stage;
+        st = hip_status(hipMemcpyAsync(stage, h_files[i] + rec_lo, rspan, hipMemcpyHostToDevice, s));
+        stage += rsg::mixed::stage_round(rspan);
+    }
+    return st;
+}
+
+// ---- mixed-length batch GET (rs_mixed_decode.hip, rs_mixed_decode_plan.h) ----
 
 // Stripes d[0 .. count) of a validated list on stream s, to the end (the
 // stream is waited for): shard i's record of stripe j at d_files[i] +
@@ -2346,75 +2468,21 @@ int decode_mixed_run(rsg_ctx* ctx, int k, int m, const rsg::mixed::RecordDesc* d
     if (mx::decode_kernel_geometry(k, m)) {
         std::shared_ptr<Codec> cd;
         if (m > 0 && !(cd = get_codec(k, m))) return RSG_ERR_INVALID_ARG;
-        const uint64_t* key = hash_key(algo);
-        const size_t fbytes = (size_t)mx::stage_round((uint64_t)count * T);
-        const size_t mbytes = (size_t)mx::stage_round((uint64_t)count * 4);
-        const size_t tbytes = count * sizeof(mx::DecDesc);
-        std::unique_ptr<rsg_ctx::MixedTab> mt = ctx->take_mixed_tab();
-        if (!mt) return RSG_ERR_DEVICE;
-        if ((st = mt->buf.ensure(fbytes + mbytes + tbytes, fbytes + mbytes + tbytes))) return st;
-        uint8_t* d_flags = mt->buf.d;
-        uint32_t* d_mis = (uint32_t*)(mt->buf.d + fbytes);
-        uint8_t* d_tab = mt->buf.d + fbytes + mbytes;
-        const uint8_t* h_flags = mt->buf.h;
-        const uint32_t* h_mis = (const uint32_t*)(mt->buf.h + fbytes);
-        uint8_t* h_tab = mt->buf.h + fbytes + mbytes;
-        st = hip_status(hipMemsetAsync(d_mis, 0, mbytes, s));
-
-        std::vector<uint32_t> todo(count), redo;
-        for (size_t j = 0; j < count; ++j) todo[j] = (uint32_t)j;
-        std::vector<mx::MaskGroup> groups;
-        std::vector<mx::DecDesc> tab;
-        std::vector<uint8_t> flags((size_t)count * T, 1);  // by shard
-        mx::MaskPlan mp;
-        struct Launch {
-            rsg::DecodeMixedParams p;
-            size_t at, n;
-            int row_shard[mx::kDecMaxC + mx::kDecMaxR];
-        };
-        std::vector<Launch> launches;
-        while (!st && !todo.empty()) {
-            mx::group_by_mask(masks.data(), todo, groups);
-            launches.clear();
-            size_t at = 0;
-            for (const mx::MaskGroup& g : groups) {
-                if (!mx::plan_mask(k, m, g.mask, verify_surplus, mp)) continue;  // TOO_FEW: no launch
-                launches.emplace_back();
-                Launch& l = launches.back();
-                if ((st = decode_mixed_params(cd.get(), k, m, g.mask, mp, d_files, d_out, key, d_flags, d_mis, l.p,
-                                              l.row_shard)))
-                    break;
-                mx::order_group_for_kernel(d, g.stripes, 0, rec_lo, out_lo, tab);
-                std::memcpy(h_tab + at * sizeof(mx::DecDesc), tab.data(), tab.size() * sizeof(mx::DecDesc));
-                l.at = at;
-                l.n = tab.size();
-                at += tab.size();
-            }
-            if (st || launches.empty()) break;
-            st = hip_status(hipMemcpyAsync(d_tab, h_tab, at * sizeof(mx::DecDesc), hipMemcpyHostToDevice, s));
-            for (size_t i = 0; i < launches.size() && !st; ++i)
-                st = hip_status(rsg::launch_decode_mixed(
-                    launches[i].p, (const mx::DecDesc*)(d_tab + launches[i].at * sizeof(mx::DecDesc)), launches[i].n, s));
-            if (!st) st = hip_status(hipMemcpyAsync(mt->buf.h, mt->buf.d, fbytes + mbytes, hipMemcpyDeviceToHost, s));
-            if (!st) st = hip_status(hipStreamSynchronize(s));
-            if (st) break;
-            // the kernel's flags are by row: to shard indices, for the planner
-            size_t li = 0;
-            for (const mx::MaskGroup& g : groups) {
-                if (mx::popcount32(g.mask) < k) continue;
-                const Launch& l = launches[li++];
-                for (uint32_t j : g.stripes)
-                    for (int row = 0; row < (int)(l.p.C + l.p.R); ++row)
-                        if (l.row_shard[row] >= 0)
-                            flags[(size_t)j * T + l.row_shard[row]] = h_flags[(size_t)j * T + row];
-            }
-            mx::redo_from_flags(k, m, verify_surplus, groups, 0, flags.data(), (size_t)T, masks.data(), redo);
-            todo.swap(redo);
-        }
-        if (!st)
-            for (size_t j = 0; j < count; ++j) mismatch[j] = h_mis[j] != 0;
-        if (st) (void)hipStreamSynchronize(s);
-        ctx->give_mixed_tab(std::move(mt), s);
+        st = record_rounds(
+            ctx, cd.get(), k, m, mx::get_out_rule(k), d, count, rec_lo, out_lo, d_files, hash_key(algo), 0, masks.data(),
+            [&](uint32_t mask, mx::MaskPlan& mp) { return mx::plan_mask(k, m, mask, verify_surplus, mp); },
+            [&](const mx::MaskPlan& mp, rsg::DecodeMixedParams& p) -> int {
+                if (mp.rows() > mx::kDecMaxR) return RSG_ERR_UNSUPPORTED;
+                p.out = d_out;
+                for (size_t r = 0; r < mp.written.size(); ++r) p.lost[r] = (uint32_t)mp.written[r];
+                return RSG_OK;
+            },
+            rsg::launch_decode_mixed,
+            [&](const uint32_t* h_mis, uint8_t*, uint8_t*) -> int {
+                for (size_t j = 0; j < count; ++j) mismatch[j] = h_mis[j] != 0;
+                return RSG_OK;
+            },
+            s);
         if (st) return st;
     } else {
         // m > 4 or k > 16: the per-length engine, stripe by stripe
@@ -2488,46 +2556,22 @@ int rsg_decode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record
     const mx::RecordDesc* desc = reinterpret_cast<const mx::RecordDesc*>(h_desc);
     const int T = k + m;
     const uint32_t data_bits = k >= 32 ? 0xffffffffu : (1u << k) - 1u;
-    std::vector<mx::DecSubBatch> subs;
-    mx::split_decode(k, T, n, desc, RSG_MIXED_STAGE_BYTES, n, subs);
+    const mx::OutRule rule = mx::get_out_rule(k);
+    std::vector<mx::RecSubBatch> subs;
+    mx::split_records(rule, T, n, desc, RSG_MIXED_STAGE_BYTES, n, subs);
     uint64_t need = RSG_MIXED_STAGE_BYTES;  // a stripe larger than that grows the stage
-    for (const auto& b : subs) need = std::max(need, mx::decode_stage_bytes(b, T));
-    // The kernel's geometries stage through the host-batch slots (pipe_mu held
-    // to the end: the call is synchronous).  The per-length engine keeps its
-    // own tickets under pipe_mu, so the other geometries stage through a
-    // buffer of the call's own on the null stream.
-    const bool slots = mx::decode_kernel_geometry(k, m);
-    std::unique_lock<std::mutex> g(ctx->pipe_mu, std::defer_lock);
-    struct Own {
-        uint8_t* d = nullptr;
-        ~Own() {
-            if (d) (void)hipFree(d);
-        }
-    } own;
-    if (slots) {
-        g.lock();
-        if ((st = ctx->ensure_pipeline((size_t)need))) return st;
-    } else if ((st = hip_status(hipMalloc((void**)&own.d, (size_t)need)))) {
-        return st;
-    }
-    PipeRun run{ctx};
+    for (const auto& b : subs) need = std::max(need, mx::record_stage_bytes(rule, b, T));
+    RecordStaging sg(ctx, mx::decode_kernel_geometry(k, m));
+    if ((st = sg.open((size_t)need))) return st;
     std::vector<uint32_t> masks;
     for (const auto& b : subs) {
         // one slot at a time: a sub-batch's verdicts decide what comes back
-        const int slot = slots ? run.next_slot() : 0;
-        hipStream_t s = slots ? ctx->pipe_stream[slot] : nullptr;
-        uint8_t* stage = slots ? ctx->d_stage[slot] : own.d;
+        sg.next_sub_batch();
+        hipStream_t s = sg.s;
+        uint8_t* stage = sg.stage;
         const uint64_t rspan = b.rec_hi - b.rec_lo, ospan = b.out_hi - b.out_lo;
-        uint32_t may = 0;  // arenas some stripe of the sub-batch may read
-        for (size_t j = 0; j < b.count; ++j) may |= desc[b.first + j].present;
         const uint8_t* dfiles[32] = {};
-        uint8_t* at = stage;
-        for (int i = 0; i < T && !st; ++i) {
-            if (!h_files[i] || !(may >> i & 1u)) continue;
-            dfiles[i] = at;
-            st = hip_status(hipMemcpyAsync(at, h_files[i] + b.rec_lo, rspan, hipMemcpyHostToDevice, s));
-            at += mx::stage_round(rspan);
-        }
+        st = upload_may_read(T, desc + b.first, b.count, h_files, 0, b.rec_lo, rspan, stage, s, dfiles);
         uint8_t* dout = stage + (uint64_t)T * mx::stage_round(rspan);
         masks.assign(b.count, 0);
         if (!st)
@@ -2560,46 +2604,6 @@ int rsg_decode_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record
 
 namespace {
 
-// The kernel's arguments for one mask group: sources, then the targets' and
-// the surplus shards' coefficient rows (plan_row over the codec's DecodePlan
-// of the readable non-target shards).
-int heal_mixed_params(Codec* cd, int k, int m, uint32_t mask, const rsg::mixed::HealPlan& hp,
-                      const uint8_t* const* d_files, uint8_t* const* d_targets, const uint64_t* key, uint8_t* d_flags,
-                      uint32_t* d_mismatch, rsg::HealMixedParams& p, int* row_shard) {
-    std::memset(&p, 0, sizeof(p));
-    const int e = (int)hp.tgt.size(), R = hp.rows();
-    if (!rsg::mixed::heal_kernel_shape(k, R) || e < 1) return RSG_ERR_UNSUPPORTED;
-    p.C = (uint32_t)k;
-    p.R = (uint32_t)R;
-    p.e = (uint32_t)e;
-    p.fstride = (uint32_t)(k + m);
-    p.flags = d_flags;
-    p.mismatch = d_mismatch;
-    std::memcpy(p.key, key, sizeof(p.key));
-    for (int c = 0; c < k; ++c) {
-        p.file[c] = d_files[hp.src[c]];
-        row_shard[c] = hp.src[c];
-    }
-    std::vector<uint8_t> present((size_t)(k + m), 0);
-    for (int i = 0; i < k + m; ++i) present[i] = (mask >> i & 1u) ? 1 : 0;
-    std::shared_ptr<DecodePlan> plan = cd->plan(present.data());
-    if (!plan) return RSG_ERR_TOO_FEW_SHARDS;
-    std::vector<uint8_t> row((size_t)k);
-    for (int r = 0; r < R; ++r) {
-        const int shard = r < e ? hp.tgt[r] : hp.surplus[r - e];
-        if (r < e) {
-            p.target[r] = d_targets[shard];
-            row_shard[k + r] = -1;
-        } else {
-            p.file[k + r] = d_files[shard];
-            row_shard[k + r] = shard;
-        }
-        plan_row(*cd, *plan, shard, row.data());
-        for (int c = 0; c < k; ++c) coef_tables(row[c], p.tab[r][c]);
-    }
-    return RSG_OK;
-}
-
 // Stripes d[0 .. count) of a validated list on stream s, to the end (the
 // stream is waited for): shard i's record of stripe j at d_files[i] +
 // d[j].rec_off - rec_lo (d_files[i] null: absent), target i's record at
@@ -2625,97 +2629,38 @@ int heal_mixed_run(rsg_ctx* ctx, int k, int m, const rsg::mixed::RecordDesc* d, 
     if (mx::heal_kernel_geometry(k, m)) {
         std::shared_ptr<Codec> cd = get_codec(k, m);
         if (!cd) return RSG_ERR_INVALID_ARG;
-        const uint64_t* key = hash_key(algo);
-        const size_t fbytes = (size_t)mx::stage_round((uint64_t)count * T);
-        const size_t mbytes = (size_t)mx::stage_round((uint64_t)count * 4);
-        const size_t obytes = (size_t)mx::stage_round((uint64_t)count * 8);
-        const size_t tbytes = count * sizeof(mx::DecDesc);
-        std::unique_ptr<rsg_ctx::MixedTab> mt = ctx->take_mixed_tab();
-        if (!mt) return RSG_ERR_DEVICE;
-        if ((st = mt->buf.ensure(fbytes + mbytes + obytes + tbytes, fbytes + mbytes + obytes + tbytes))) return st;
-        uint8_t* d_flags = mt->buf.d;
-        uint32_t* d_mis = (uint32_t*)(mt->buf.d + fbytes);
-        uint8_t* d_offs = mt->buf.d + fbytes + mbytes;
-        uint8_t* d_tab = d_offs + obytes;
-        const uint8_t* h_flags = mt->buf.h;
-        const uint32_t* h_mis = (const uint32_t*)(mt->buf.h + fbytes);
-        uint64_t* h_offs = (uint64_t*)(mt->buf.h + fbytes + mbytes);
-        uint8_t* h_tab = mt->buf.h + fbytes + mbytes + obytes;
-        st = hip_status(hipMemsetAsync(d_mis, 0, mbytes, s));
-
-        std::vector<uint32_t> todo(count), redo;
-        for (size_t j = 0; j < count; ++j) todo[j] = (uint32_t)j;
-        std::vector<mx::MaskGroup> groups;
-        std::vector<mx::DecDesc> tab;
-        std::vector<uint8_t> flags((size_t)count * T, 1);  // by shard
-        mx::HealPlan hp;
-        struct Launch {
-            rsg::HealMixedParams p;
-            size_t at, n;
-            int row_shard[mx::kDecMaxC + mx::kDecMaxR];
-        };
-        std::vector<Launch> launches;
-        while (!st && !todo.empty()) {
-            mx::group_by_mask(masks.data(), todo, groups);
-            launches.clear();
-            size_t at = 0;
-            for (const mx::MaskGroup& g : groups) {
-                if (!mx::plan_heal_mask(k, m, g.mask, targets, hp)) continue;  // TOO_FEW: no launch
-                launches.emplace_back();
-                Launch& l = launches.back();
-                if ((st = heal_mixed_params(cd.get(), k, m, g.mask, hp, d_files, d_targets, key, d_flags, d_mis, l.p,
-                                            l.row_shard)))
-                    break;
-                mx::order_heal_group_for_kernel(d, g.stripes, 0, rec_lo, out_lo, tab);
-                std::memcpy(h_tab + at * sizeof(mx::DecDesc), tab.data(), tab.size() * sizeof(mx::DecDesc));
-                l.at = at;
-                l.n = tab.size();
-                at += tab.size();
-            }
-            if (st || launches.empty()) break;
-            st = hip_status(hipMemcpyAsync(d_tab, h_tab, at * sizeof(mx::DecDesc), hipMemcpyHostToDevice, s));
-            for (size_t i = 0; i < launches.size() && !st; ++i)
-                st = hip_status(rsg::launch_heal_mixed(
-                    launches[i].p, (const mx::DecDesc*)(d_tab + launches[i].at * sizeof(mx::DecDesc)), launches[i].n, s));
-            if (!st) st = hip_status(hipMemcpyAsync(mt->buf.h, mt->buf.d, fbytes + mbytes, hipMemcpyDeviceToHost, s));
-            if (!st) st = hip_status(hipStreamSynchronize(s));
-            if (st) break;
-            // the kernel's flags are by row: to shard indices, for the planner
-            size_t li = 0;
-            for (const mx::MaskGroup& g : groups) {
-                if (!mx::plan_heal_mask(k, m, g.mask, targets, hp)) continue;
-                const Launch& l = launches[li++];
-                for (uint32_t j : g.stripes)
-                    for (int row = 0; row < (int)(l.p.C + l.p.R); ++row)
-                        if (l.row_shard[row] >= 0)
-                            flags[(size_t)j * T + l.row_shard[row]] = h_flags[(size_t)j * T + row];
-            }
-            mx::redo_heal_from_flags(k, m, targets, groups, 0, flags.data(), (size_t)T, masks.data(), redo);
-            todo.swap(redo);
-        }
-        // verdicts; the failed stripes' target headers zeroed in one launch
-        // (a first round may already have written a digest there)
-        size_t nfail = 0;
-        if (!st) {
-            for (size_t j = 0; j < count; ++j) {
-                h_status[j] = mx::popcount32(masks[j]) < k ? RSG_ERR_TOO_FEW_SHARDS
-                              : h_mis[j]                   ? RSG_ERR_INCONSISTENT_SOURCES
-                                                           : RSG_OK;
-                if (h_status[j] != RSG_OK) h_offs[nfail++] = d[j].out_off - out_lo;
-            }
-        }
-        if (!st && nfail) {
-            rsg::HealZeroParams z;
-            std::memset(&z, 0, sizeof(z));
-            for (int i = 0; i < T; ++i)
-                if (d_targets[i]) z.target[z.nt++] = d_targets[i];
-            st = hip_status(hipMemcpyAsync(d_offs, h_offs, nfail * 8, hipMemcpyHostToDevice, s));
-            if (!st) st = hip_status(rsg::launch_heal_zero_headers(z, (const uint64_t*)d_offs, nfail, s));
-            if (!st) st = hip_status(hipStreamSynchronize(s));
-        }
-        if (st) (void)hipStreamSynchronize(s);
-        ctx->give_mixed_tab(std::move(mt), s);
-        return st;
+        return record_rounds(
+            ctx, cd.get(), k, m, mx::heal_out_rule(mx::popcount32(targets)), d, count, rec_lo, out_lo, d_files,
+            hash_key(algo), (size_t)mx::stage_round((uint64_t)count * 8), masks.data(),
+            [&](uint32_t mask, mx::MaskPlan& mp) { return mx::plan_heal_mask(k, m, mask, targets, mp); },
+            [&](const mx::MaskPlan& mp, rsg::HealMixedParams& p) -> int {
+                if (!mx::heal_kernel_shape(k, mp.rows()) || mp.written.empty()) return RSG_ERR_UNSUPPORTED;
+                for (size_t r = 0; r < mp.written.size(); ++r) p.target[r] = d_targets[mp.written[r]];
+                return RSG_OK;
+            },
+            rsg::launch_heal_mixed,
+            // verdicts; the failed stripes' target headers zeroed in one launch
+            // (a first round may already have written a digest there)
+            [&](const uint32_t* h_mis, uint8_t* d_offs, uint8_t* h_extra) -> int {
+                uint64_t* h_offs = (uint64_t*)h_extra;
+                size_t nfail = 0;
+                for (size_t j = 0; j < count; ++j) {
+                    h_status[j] = mx::popcount32(masks[j]) < k ? RSG_ERR_TOO_FEW_SHARDS
+                                  : h_mis[j]                   ? RSG_ERR_INCONSISTENT_SOURCES
+                                                               : RSG_OK;
+                    if (h_status[j] != RSG_OK) h_offs[nfail++] = d[j].out_off - out_lo;
+                }
+                if (!nfail) return RSG_OK;
+                rsg::HealZeroParams z;
+                std::memset(&z, 0, sizeof(z));
+                for (int i = 0; i < T; ++i)
+                    if (d_targets[i]) z.target[z.nt++] = d_targets[i];
+                int zs = hip_status(hipMemcpyAsync(d_offs, h_offs, nfail * 8, hipMemcpyHostToDevice, s));
+                if (!zs) zs = hip_status(rsg::launch_heal_zero_headers(z, (const uint64_t*)d_offs, nfail, s));
+                if (!zs) zs = hip_status(hipStreamSynchronize(s));
+                return zs;
+            },
+            s);
     }
     // m > 4 or k > 16: the per-length engine, stripe by stripe (it zeroes the
     // headers of a stripe it fails); an empty stripe is judged by its mask
@@ -2785,55 +2730,31 @@ int rsg_heal_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_d
     if (st || n == 0) return st;
     const mx::RecordDesc* desc = reinterpret_cast<const mx::RecordDesc*>(h_desc);
     const int T = k + m;
-    int nt = 0, nf = 0;  // targets; arenas that may be read
+    int nf = 0;  // arenas that may be read
+    uint32_t targets = 0;
     for (int i = 0; i < T; ++i) {
-        if (h_targets[i]) ++nt;
+        if (h_targets[i]) targets |= 1u << i;
         else if (h_files[i]) ++nf;
     }
-    std::vector<mx::HealSubBatch> subs;
-    mx::split_heal(nf, nt, n, desc, RSG_MIXED_STAGE_BYTES, n, subs);
+    const mx::OutRule rule = mx::heal_out_rule(mx::popcount32(targets));
+    std::vector<mx::RecSubBatch> subs;
+    mx::split_records(rule, nf, n, desc, RSG_MIXED_STAGE_BYTES, n, subs);
     uint64_t need = RSG_MIXED_STAGE_BYTES;  // a stripe larger than that grows the stage
-    for (const auto& b : subs) need = std::max(need, mx::heal_stage_bytes(b, nf, nt));
-    // As rsg_decode_mixed_host: the kernel's geometries stage through the
-    // host-batch slots (pipe_mu held to the end: the call is synchronous); the
-    // per-length engine keeps its own tickets under pipe_mu, so the other
-    // geometries stage through a buffer of the call's own on the null stream.
-    const bool slots = mx::heal_kernel_geometry(k, m);
-    std::unique_lock<std::mutex> g(ctx->pipe_mu, std::defer_lock);
-    struct Own {
-        uint8_t* d = nullptr;
-        ~Own() {
-            if (d) (void)hipFree(d);
-        }
-    } own;
-    if (slots) {
-        g.lock();
-        if ((st = ctx->ensure_pipeline((size_t)need))) return st;
-    } else if ((st = hip_status(hipMalloc((void**)&own.d, (size_t)need)))) {
-        return st;
-    }
-    PipeRun run{ctx};
+    for (const auto& b : subs) need = std::max(need, mx::record_stage_bytes(rule, b, nf));
+    RecordStaging sg(ctx, mx::heal_kernel_geometry(k, m));
+    if ((st = sg.open((size_t)need))) return st;
     const int fail_at = ctx->fail_subbatch.load();  // rsg_test_fail_subbatch (tests only)
     int sub = 0;
     for (const auto& b : subs) {
         // A sub-batch's verdicts need its stream waited for (heal_mixed_run);
         // its copies back then overlap the next sub-batch on the next slot.
-        const int slot = slots ? run.next_slot() : 0;
-        hipStream_t s = slots ? ctx->pipe_stream[slot] : nullptr;
-        uint8_t* stage = slots ? ctx->d_stage[slot] : own.d;
+        sg.next_sub_batch();
+        hipStream_t s = sg.s;
         const uint64_t rspan = b.rec_hi - b.rec_lo, ospan = b.out_hi - b.out_lo;
-        uint32_t may = 0;  // arenas some stripe of the sub-batch may read
-        for (size_t j = 0; j < b.count; ++j) may |= desc[b.first + j].present;
         const uint8_t* dfiles[32] = {};
         uint8_t* dtargets[32] = {};
-        uint8_t* at = stage;
-        for (int i = 0; i < T && !st; ++i) {
-            if (h_targets[i] || !h_files[i] || !(may >> i & 1u)) continue;
-            dfiles[i] = at;
-            st = hip_status(hipMemcpyAsync(at, h_files[i] + b.rec_lo, rspan, hipMemcpyHostToDevice, s));
-            at += mx::stage_round(rspan);
-        }
-        at = stage + (uint64_t)nf * mx::stage_round(rspan);
+        st = upload_may_read(T, desc + b.first, b.count, h_files, targets, b.rec_lo, rspan, sg.stage, s, dfiles);
+        uint8_t* at = sg.stage + (uint64_t)nf * mx::stage_round(rspan);
         for (int i = 0; i < T; ++i) {
             if (!h_targets[i]) continue;
             dtargets[i] = at;
@@ -2847,15 +2768,15 @@ int rsg_heal_mixed_host(rsg_ctx* ctx, int k, int m, size_t n, const rsg_record_d
         for (int i = 0; i < T && !st; ++i)
             if (h_targets[i])
                 st = hip_status(hipMemcpyAsync(h_targets[i] + b.out_lo, dtargets[i], ospan, hipMemcpyDeviceToHost, s));
-        if (!slots) {
+        if (!sg.slots) {
             const int sy = hip_status(hipStreamSynchronize(s));
             if (!st) st = sy;
         }
         if (st) break;
     }
     // nothing of the call is in flight when it returns, whatever its status
-    for (int b = 0; slots && b < rsg_ctx::kPipeSlots; ++b) {
-        if (!run.used[b]) continue;
+    for (int b = 0; sg.slots && b < rsg_ctx::kPipeSlots; ++b) {
+        if (!sg.run.used[b]) continue;
         const int sy = hip_status(hipStreamSynchronize(ctx->pipe_stream[b]));
         if (!st) st = sy;
     }

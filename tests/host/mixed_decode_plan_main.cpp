@@ -1,23 +1,12 @@
 // Stand-alone check of the mixed-length GET's host planner
 // (rustfs_amd/csrc/rs_mixed_decode_plan.h), built by the host compiler with
 // AddressSanitizer + UBSan and run directly (tests/test_mixed_decode_plan.py).
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <set>
 #include <vector>
 
-#include "../../rustfs_amd/csrc/rs_mixed_decode_plan.h"
+#include "record_rounds_check.h"  // CHECK, run_rounds; the planner header
 
 using namespace rsg::mixed;
-
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "%s:%d: CHECK(%s)\n", __FILE__, __LINE__, #c); \
-            exit(1);                                                  \
-        }                                                             \
-    } while (0)
 
 namespace {
 
@@ -119,26 +108,26 @@ void test_plans() {
     MaskPlan p;
     // RS(4,2), all present: nothing rebuilt, no parity read
     CHECK(plan_mask(4, 2, 0x3f, true, p));
-    CHECK(p.src == std::vector<int>({0, 1, 2, 3}) && p.lost.empty() && p.surplus.empty());
+    CHECK(p.src == std::vector<int>({0, 1, 2, 3}) && p.written.empty() && p.surplus.empty());
     CHECK(p.read_mask() == 0xfu);
     // data shard 1 absent: sources 0 2 3 4, surplus 5 (only with verify_surplus)
     CHECK(plan_mask(4, 2, 0x3d, true, p));
-    CHECK(p.src == std::vector<int>({0, 2, 3, 4}) && p.lost == std::vector<int>({1}) &&
+    CHECK(p.src == std::vector<int>({0, 2, 3, 4}) && p.written == std::vector<int>({1}) &&
           p.surplus == std::vector<int>({5}));
     CHECK(p.read_mask() == 0x3du);
     CHECK(plan_mask(4, 2, 0x3d, false, p));
     CHECK(p.surplus.empty() && p.read_mask() == 0x1du);
     // exactly k, then k - 1
     CHECK(plan_mask(4, 2, 0x35, true, p));
-    CHECK(p.src == std::vector<int>({0, 2, 4, 5}) && p.lost == std::vector<int>({1, 3}) && p.surplus.empty());
+    CHECK(p.src == std::vector<int>({0, 2, 4, 5}) && p.written == std::vector<int>({1, 3}) && p.surplus.empty());
     CHECK(!plan_mask(4, 2, 0x31, true, p));
     CHECK(!plan_mask(4, 2, 0, true, p));
     CHECK(plan_mask(5, 0, 0x1f, true, p));  // m = 0 only verifies
-    CHECK(p.lost.empty() && p.surplus.empty());
+    CHECK(p.written.empty() && p.surplus.empty());
     CHECK(!plan_mask(5, 0, 0x1e, true, p));
     // the computed rows never exceed m
     for (uint32_t mask = 0; mask < (1u << 12); ++mask)
-        if (plan_mask(8, 4, mask, true, p)) CHECK(p.lost.size() + p.surplus.size() <= 4 && p.src.size() == 8);
+        if (plan_mask(8, 4, mask, true, p)) CHECK(p.written.size() + p.surplus.size() <= 4 && p.src.size() == 8);
     CHECK(decode_kernel_geometry(16, 4) && decode_kernel_geometry(5, 0) && !decode_kernel_geometry(10, 6) &&
           !decode_kernel_geometry(17, 3));
 }
@@ -173,7 +162,7 @@ void test_grouping_and_order() {
         MaskPlan p;
         CHECK(plan_mask(k, m, gr.mask, true, p) == (gr.mask != C));  // fewer than k bits: no launch
         std::vector<DecDesc> tab;
-        order_group_for_kernel(d.data(), gr.stripes, 0, d[0].rec_off, 3, tab);
+        order_group_for_kernel(get_out_rule(k), d.data(), gr.stripes, 0, d[0].rec_off, 3, tab);
         CHECK(tab.size() == gr.stripes.size());
         std::set<uint32_t> jobs;
         for (size_t i = 0; i < tab.size(); ++i) {
@@ -190,7 +179,7 @@ void test_grouping_and_order() {
     // a sub-batch's jobs are relative to its first stripe
     std::vector<uint32_t> part = {5, 6, 7};
     std::vector<DecDesc> tab;
-    order_group_for_kernel(d.data(), part, 5, d[5].rec_off, 0, tab);
+    order_group_for_kernel(get_out_rule(k), d.data(), part, 5, d[5].rec_off, 0, tab);
     for (const DecDesc& x : tab) CHECK(x.job < 3 && x.len == d[5 + x.job].shard_len);
     // an empty todo list
     group_by_mask(masks.data(), {}, g);
@@ -204,14 +193,15 @@ void test_split() {
     lens[20] = 300000;  // larger than the stage: a sub-batch of its own
     std::vector<RecordDesc> d = make(k, lens, {0x3f});
     const uint64_t stage = 200000;
-    std::vector<DecSubBatch> subs;
-    split_decode(k, t, d.size(), d.data(), stage, d.size(), subs);
+    const OutRule rule = get_out_rule(k);
+    std::vector<RecSubBatch> subs;
+    split_records(rule, t, d.size(), d.data(), stage, d.size(), subs);
     size_t next = 0;
     bool alone = false;
-    for (const DecSubBatch& b : subs) {
+    for (const RecSubBatch& b : subs) {
         CHECK(b.first == next && b.count >= 1);
         next += b.count;
-        CHECK(b.count == 1 || decode_stage_bytes(b, t) <= stage);
+        CHECK(b.count == 1 || record_stage_bytes(rule, b, t) <= stage);
         if (b.first == 20) alone = b.count == 1;
         CHECK(b.rec_lo == d[b.first].rec_off);
         const RecordDesc& last = d[b.first + b.count - 1];
@@ -222,19 +212,20 @@ void test_split() {
         }
     }
     CHECK(next == d.size() && alone && subs.size() >= 3);
-    split_decode(k, t, d.size(), d.data(), UINT64_MAX, d.size(), subs);
+    split_records(rule, t, d.size(), d.data(), UINT64_MAX, d.size(), subs);
     CHECK(subs.size() == 1 && subs[0].count == d.size());
-    split_decode(k, t, d.size(), d.data(), UINT64_MAX, 7, subs);  // max_count
+    split_records(rule, t, d.size(), d.data(), UINT64_MAX, 7, subs);  // max_count
     CHECK(subs.size() == 6 && subs.back().count == 5);
-    split_decode(k, t, 0, d.data(), stage, 1, subs);
+    split_records(rule, t, 0, d.data(), stage, 1, subs);
     CHECK(subs.empty());
     auto z = make(k, {0, 0, 0}, {0x3f});  // only empty stripes: no out span
-    split_decode(k, t, z.size(), z.data(), stage, z.size(), subs);
+    split_records(rule, t, z.size(), z.data(), stage, z.size(), subs);
     CHECK(subs.size() == 1 && subs[0].out_lo == 0 && subs[0].out_hi == 0 && subs[0].rec_hi > subs[0].rec_lo);
 }
 
-// Rounds of launch -> flags -> regrouping, driven by a table of records that
-// are rotten; ends in at most k+m rounds with the verified sets.
+// The rounds the library runs (plan_round -> launches -> shard_flags_from_rows
+// -> redo_from_flags), driven by a table of records that are rotten; ends in
+// at most k+m rounds with the verified sets.
 void test_redo() {
     const int k = 4, m = 2, t = k + m;
     const size_t n = 9;
@@ -242,30 +233,10 @@ void test_redo() {
     const uint32_t rotten[n] = {0, 0x02, 0x10, 0x20, 0x3f, 0x0f, 0x01, 0x12, 0};
     uint32_t masks[n] = {0x3f, 0x3f, 0x3d, 0x3d, 0x3f, 0x3f, 0x07, 0x3f, 0x3e};
     const uint32_t start[n] = {0x3f, 0x3f, 0x3d, 0x3d, 0x3f, 0x3f, 0x07, 0x3f, 0x3e};
-    std::vector<uint32_t> todo(n), redo;
-    for (size_t i = 0; i < n; ++i) todo[i] = (uint32_t)i;
-    std::vector<uint8_t> flags(n * t, 1);
-    std::vector<MaskGroup> groups;
-    int rounds = 0;
-    while (!todo.empty()) {
-        CHECK(++rounds <= t + 1);  // the last round finds nothing to redo
-        group_by_mask(masks, todo, groups);
-        MaskPlan p;
-        for (const MaskGroup& g : groups) {
-            if (!plan_mask(k, m, g.mask, true, p)) continue;
-            for (uint32_t s : g.stripes)  // what the kernel would write: one flag per row read
-                for (int i = 0; i < t; ++i)
-                    if (p.read_mask() >> i & 1u) flags[s * t + (size_t)i] = (rotten[s] >> i & 1u) ? 0 : 1;
-        }
-        std::vector<uint32_t> before(masks, masks + n);
-        redo_from_flags(k, m, true, groups, 0, flags.data(), (size_t)t, masks, redo);
-        for (size_t i = 0; i < redo.size(); ++i) {
-            CHECK(i == 0 || redo[i - 1] < redo[i]);
-            CHECK(popcount32(masks[redo[i]]) < popcount32(before[redo[i]]));  // at least one bit fewer
-        }
-        for (size_t s = 0; s < n; ++s) CHECK((masks[s] & ~before[s]) == 0);
-        todo = redo;
-    }
+    const std::vector<RecordDesc> d = make(k, {7, 0, 513, 64, 1025, 1, 0, 300, 65}, {0x3f});
+    const int rounds = rounds_check::run_rounds(k, m, get_out_rule(k), d, rotten, masks, [&](uint32_t mask, MaskPlan& p) {
+        return plan_mask(k, m, mask, true, p);
+    });
     CHECK(rounds <= t);
     for (size_t s = 0; s < n; ++s) {
         // no record that was read and failed stays; nothing healthy is dropped
@@ -281,6 +252,42 @@ void test_redo() {
     CHECK(masks[7] == 0x2d);  // parity 4 is found rotten only after data 1 is
 }
 
+// A round that mixes groups with a plan and a group with fewer than k readable
+// shards, which has no launch: the flags of each launch go to its own group's
+// stripes.  RS(4,2), three masks interleaved in groups of SPW+1, SPW and 1
+// stripes, the one without a plan first met between the other two.
+void test_rounds_beside_a_group_without_launch() {
+    const int k = 4, m = 2, t = k + m, spw = decode_spw_for(t);
+    const uint32_t A = 0x3f, B = 0x3d, C = 0x07;  // C: three bits set
+    std::vector<uint32_t> masks, rotten, lens;
+    for (int i = 0; i < spw + 1; ++i) {
+        masks.push_back(B);
+        rotten.push_back(i == 1 ? 0x10u : i == spw ? 0x01u : 0u);  // a source parity; a data source
+        if (i < spw) {
+            masks.push_back(C);
+            rotten.push_back(0x3f);  // never read
+        }
+        if (i == 1) {
+            masks.push_back(A);
+            rotten.push_back(0x02);  // joins B's mask in the second round
+        }
+    }
+    const size_t n = masks.size();
+    for (size_t i = 0; i < n; ++i) lens.push_back((uint32_t)((i * 700) % 2000));
+    const std::vector<RecordDesc> d = make(k, lens, {0x3f});
+    const std::vector<uint32_t> start = masks;
+    const int rounds = rounds_check::run_rounds(k, m, get_out_rule(k), d, rotten.data(), masks.data(),
+                                                [&](uint32_t mask, MaskPlan& p) { return plan_mask(k, m, mask, true, p); });
+    CHECK(rounds >= 2 && rounds <= t);
+    size_t moved = 0;
+    for (size_t s = 0; s < n; ++s) {
+        // no launch: untouched, whatever the launches beside it wrote
+        CHECK(masks[s] == (start[s] == C ? C : start[s] & ~rotten[s]));
+        moved += masks[s] != start[s];
+    }
+    CHECK(moved == 3);
+}
+
 }  // namespace
 
 int main() {
@@ -289,6 +296,7 @@ int main() {
     test_grouping_and_order();
     test_split();
     test_redo();
+    test_rounds_beside_a_group_without_launch();
     printf("mixed decode plan ok\n");
     return 0;
 }

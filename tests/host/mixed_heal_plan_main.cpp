@@ -1,23 +1,13 @@
 // Stand-alone check of the mixed-length heal's host planner
 // (rustfs_amd/csrc/rs_mixed_heal_plan.h), built by the host compiler with
 // AddressSanitizer + UBSan and run directly (tests/test_mixed_heal_plan.py).
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <set>
 #include <vector>
 
 #include "../../rustfs_amd/csrc/rs_mixed_heal_plan.h"
+#include "record_rounds_check.h"  // CHECK, run_rounds
 
 using namespace rsg::mixed;
-
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "%s:%d: CHECK(%s)\n", __FILE__, __LINE__, #c); \
-            exit(1);                                                  \
-        }                                                             \
-    } while (0)
 
 namespace {
 
@@ -141,19 +131,19 @@ void test_validation() {
 }
 
 void test_plans() {
-    HealPlan p;
+    MaskPlan p;
     // RS(4,2), data shard 1 the target, all others readable: sources 0 2 3 4, surplus 5
     CHECK(plan_heal_mask(4, 2, 0x3f, 1u << 1, p));  // the target's own bit is ignored
-    CHECK(p.src == std::vector<int>({0, 2, 3, 4}) && p.tgt == std::vector<int>({1}) &&
+    CHECK(p.src == std::vector<int>({0, 2, 3, 4}) && p.written == std::vector<int>({1}) &&
           p.surplus == std::vector<int>({5}));
     CHECK(p.read_mask() == 0x3du && p.rows() == 2);
     // a parity target: sources are the data, the other parity is surplus
     CHECK(plan_heal_mask(4, 2, 0x3f, 1u << 5, p));
-    CHECK(p.src == std::vector<int>({0, 1, 2, 3}) && p.tgt == std::vector<int>({5}) &&
+    CHECK(p.src == std::vector<int>({0, 1, 2, 3}) && p.written == std::vector<int>({5}) &&
           p.surplus == std::vector<int>({4}));
     // a data and a parity target: exactly k readable
     CHECK(plan_heal_mask(4, 2, 0x3f, (1u << 0) | (1u << 4), p));
-    CHECK(p.src == std::vector<int>({1, 2, 3, 5}) && p.tgt == std::vector<int>({0, 4}) && p.surplus.empty());
+    CHECK(p.src == std::vector<int>({1, 2, 3, 5}) && p.written == std::vector<int>({0, 4}) && p.surplus.empty());
     // one target and one shard absent besides
     CHECK(plan_heal_mask(4, 2, 0x3f & ~(1u << 3), 1u << 0, p));
     CHECK(p.src == std::vector<int>({1, 2, 4, 5}) && p.surplus.empty() && p.rows() == 1);
@@ -175,7 +165,7 @@ void test_plans() {
                 CHECK(ok == (popcount32(mask & ~targets) >= k));
                 if (!ok) continue;
                 ++plans;
-                CHECK((int)p.src.size() == k && (int)p.tgt.size() == e);
+                CHECK((int)p.src.size() == k && (int)p.written.size() == e);
                 CHECK(p.rows() >= 1 && p.rows() <= m && heal_kernel_shape(k, p.rows()));
                 CHECK((p.read_mask() & targets) == 0 && p.read_mask() == (mask & ~targets));
                 for (size_t i = 1; i < p.src.size(); ++i) CHECK(p.src[i - 1] < p.src[i]);
@@ -213,10 +203,10 @@ void test_grouping_and_order() {
     CHECK(g[0].stripes.size() == (size_t)spw + 1 && g[1].stripes.size() == (size_t)spw && g[2].stripes.size() == 1);
     std::set<uint32_t> seen;
     for (const MaskGroup& gr : g) {
-        HealPlan p;
+        MaskPlan p;
         CHECK(plan_heal_mask(k, m, gr.mask, targets, p) == (gr.mask != C));  // fewer than k: no launch
         std::vector<DecDesc> tab;
-        order_heal_group_for_kernel(d.data(), gr.stripes, 0, d[0].rec_off, 3, tab);
+        order_group_for_kernel(heal_out_rule(1), d.data(), gr.stripes, 0, d[0].rec_off, 3, tab);
         CHECK(tab.size() == gr.stripes.size());
         std::set<uint32_t> jobs;
         for (size_t i = 0; i < tab.size(); ++i) {
@@ -234,7 +224,7 @@ void test_grouping_and_order() {
     // a sub-batch's jobs are relative to its first stripe
     std::vector<uint32_t> part = {0, 1, 2};
     std::vector<DecDesc> tab;
-    order_heal_group_for_kernel(d.data() + 5, part, 0, d[5].rec_off, d[5].out_off, tab);
+    order_group_for_kernel(heal_out_rule(1), d.data() + 5, part, 0, d[5].rec_off, d[5].out_off, tab);
     for (const DecDesc& x : tab)
         CHECK(x.job < 3 && x.len == d[5 + x.job].shard_len && x.out_off == d[5 + x.job].out_off - d[5].out_off);
 }
@@ -246,36 +236,38 @@ void test_split() {
     lens[20] = 300000;  // larger than the stage: a sub-batch of its own
     std::vector<RecordDesc> d = make(lens, {0x3f});
     const uint64_t stage = 200000;
-    std::vector<HealSubBatch> subs;
-    split_heal(files, targets, d.size(), d.data(), stage, d.size(), subs);
+    const OutRule rule = heal_out_rule(targets);
+    std::vector<RecSubBatch> subs;
+    split_records(rule, files, d.size(), d.data(), stage, d.size(), subs);
     size_t next = 0;
     bool alone = false;
-    for (const HealSubBatch& b : subs) {
+    for (const RecSubBatch& b : subs) {
         CHECK(b.first == next && b.count >= 1);  // every stripe once, in order
         next += b.count;
-        CHECK(b.count == 1 || heal_stage_bytes(b, files, targets) <= stage);
+        CHECK(b.count == 1 || record_stage_bytes(rule, b, files) <= stage);
         if (b.first == 20) alone = b.count == 1;
         const RecordDesc& last = d[b.first + b.count - 1];
         CHECK(b.rec_lo == d[b.first].rec_off && b.rec_hi == last.rec_off + kRecHeader + last.shard_len);
         CHECK(b.out_lo == d[b.first].out_off && b.out_hi == last.out_off + kRecHeader + last.shard_len);
         // the record span once per arena, the target span once per target
-        CHECK(heal_stage_bytes(b, files, targets) ==
+        CHECK(record_stage_bytes(rule, b, files) ==
               files * stage_round(b.rec_hi - b.rec_lo) + targets * stage_round(b.out_hi - b.out_lo));
     }
     CHECK(next == d.size() && alone && subs.size() >= 3);
-    split_heal(files, targets, d.size(), d.data(), UINT64_MAX, d.size(), subs);
+    split_records(rule, files, d.size(), d.data(), UINT64_MAX, d.size(), subs);
     CHECK(subs.size() == 1 && subs[0].count == d.size());
-    split_heal(files, targets, d.size(), d.data(), UINT64_MAX, 7, subs);  // max_count
+    split_records(rule, files, d.size(), d.data(), UINT64_MAX, 7, subs);  // max_count
     CHECK(subs.size() == 6 && subs.back().count == 5);
-    split_heal(files, targets, 0, d.data(), stage, 1, subs);
+    split_records(rule, files, 0, d.data(), stage, 1, subs);
     CHECK(subs.empty());
     auto z = make({0, 0, 0}, {0x3f});  // only empty stripes: their headers are the target span
-    split_heal(files, targets, z.size(), z.data(), stage, z.size(), subs);
+    split_records(rule, files, z.size(), z.data(), stage, z.size(), subs);
     CHECK(subs.size() == 1 && subs[0].out_hi - subs[0].out_lo >= 3 * kRecHeader);
 }
 
-// Rounds of launch -> flags -> regrouping, driven by a table of records that
-// are rotten; ends in at most k+m rounds with the verified sets.
+// The rounds the library runs (plan_round -> launches -> shard_flags_from_rows
+// -> redo_from_flags), driven by a table of records that are rotten; ends in
+// at most k+m rounds with the verified sets.
 void test_redo() {
     const int k = 4, m = 2, t = k + m;
     const uint32_t targets = 1u << 1;
@@ -285,33 +277,13 @@ void test_redo() {
     const uint32_t start[n] = {0x3d, 0x3d, 0x3d, 0x3d, 0x3d, 0x3d, 0x3d, 0x1d};
     uint32_t masks[n];
     for (size_t s = 0; s < n; ++s) masks[s] = start[s];
-    std::vector<uint32_t> todo(n), redo;
-    for (size_t i = 0; i < n; ++i) todo[i] = (uint32_t)i;
-    std::vector<uint8_t> flags(n * t, 1);
-    std::vector<MaskGroup> groups;
-    int rounds = 0;
-    while (!todo.empty()) {
-        CHECK(++rounds <= t + 1);  // the last round finds nothing to redo
-        group_by_mask(masks, todo, groups);
-        HealPlan p;
-        for (const MaskGroup& g : groups) {
-            if (!plan_heal_mask(k, m, g.mask, targets, p)) continue;
-            for (uint32_t s : g.stripes)  // what the kernel would write: one flag per row read
-                for (int i = 0; i < t; ++i)
-                    if (p.read_mask() >> i & 1u) flags[s * t + (size_t)i] = (rotten[s] >> i & 1u) ? 0 : 1;
-        }
-        std::vector<uint32_t> before(masks, masks + n);
-        redo_heal_from_flags(k, m, targets, groups, 0, flags.data(), (size_t)t, masks, redo);
-        for (size_t i = 0; i < redo.size(); ++i) {
-            CHECK(i == 0 || redo[i - 1] < redo[i]);
-            CHECK(popcount32(masks[redo[i]]) < popcount32(before[redo[i]]));  // at least one bit fewer
-        }
-        for (size_t s = 0; s < n; ++s) CHECK((masks[s] & ~before[s]) == 0);
-        todo = redo;
-    }
+    const std::vector<RecordDesc> d = make({7, 0, 513, 64, 1025, 1, 0, 300}, {0x3f});
+    const int rounds = rounds_check::run_rounds(k, m, heal_out_rule(1), d, rotten, masks, [&](uint32_t mask, MaskPlan& p) {
+        return plan_heal_mask(k, m, mask, targets, p);
+    });
     CHECK(rounds <= t);
     for (size_t s = 0; s < n; ++s) {
-        HealPlan p;
+        MaskPlan p;
         if (plan_heal_mask(k, m, masks[s], targets, p)) CHECK((p.read_mask() & rotten[s]) == 0);
     }
     CHECK(masks[0] == 0x3d && masks[7] == 0x1d);
@@ -323,6 +295,45 @@ void test_redo() {
     CHECK(popcount32(masks[6]) < k);  // data 2 and parity 4: three left
 }
 
+// A round that mixes groups with a plan and a group with fewer than k readable
+// shards, which has no launch: the flags of each launch go to its own group's
+// stripes.  RS(4,2) with data shard 1 the target, three masks interleaved in
+// groups of SPW+1, SPW and 1 stripes, the one without a plan first met between
+// the other two.
+void test_rounds_beside_a_group_without_launch() {
+    const int k = 4, m = 2, t = k + m, spw = decode_spw_for(t);
+    const uint32_t targets = 1u << 1;
+    const uint32_t A = 0x3d, B = 0x2d, C = 0x0d;  // C: three bits set
+    std::vector<uint32_t> masks, rotten, lens;
+    for (int i = 0; i < spw + 1; ++i) {
+        masks.push_back(B);
+        rotten.push_back(i == spw ? 0x20u : 0u);  // a source parity: three left
+        if (i < spw) {
+            masks.push_back(C);
+            rotten.push_back(0x3f);  // never read
+        }
+        if (i == 1) {
+            masks.push_back(A);
+            rotten.push_back(0x10);  // joins B's mask in the second round
+        }
+    }
+    const size_t n = masks.size();
+    for (size_t i = 0; i < n; ++i) lens.push_back((uint32_t)((i * 700) % 2000));
+    const std::vector<RecordDesc> d = make(lens, {0x3f});
+    const std::vector<uint32_t> start = masks;
+    const int rounds = rounds_check::run_rounds(
+        k, m, heal_out_rule(1), d, rotten.data(), masks.data(),
+        [&](uint32_t mask, MaskPlan& p) { return plan_heal_mask(k, m, mask, targets, p); });
+    CHECK(rounds >= 2 && rounds <= t);
+    size_t moved = 0;
+    for (size_t s = 0; s < n; ++s) {
+        // no launch: untouched, whatever the launches beside it wrote
+        CHECK(masks[s] == (start[s] == C ? C : start[s] & ~rotten[s]));
+        moved += masks[s] != start[s];
+    }
+    CHECK(moved == 2);
+}
+
 }  // namespace
 
 int main() {
@@ -331,6 +342,7 @@ int main() {
     test_grouping_and_order();
     test_split();
     test_redo();
+    test_rounds_beside_a_group_without_launch();
     printf("mixed heal plan ok\n");
     return 0;
 }
