@@ -415,8 +415,10 @@ int rsg_encode_mixed_host_submit(rsg_ctx *ctx, int k, int m, size_t n, const rsg
  * The call leaves alone every byte of `out` outside the windows of rebuilt
  * shards (the gaps and the windows of served shards included) and every byte
  * of the sources.  The window of a data shard that `present` or a NULL arena
- * declares absent is written before the stripe's verdict is known, so it holds
- * unspecified bytes when the stripe fails.
+ * declares absent, or whose record fails its hash, is written before the
+ * stripe's verdict is known, so it holds unspecified bytes when the stripe
+ * fails (rsg_decode_mixed_dev; the host form copies nothing back for a failed
+ * stripe).
  * RSG_ERR_INVALID_ARG with nothing written: a `present` bit at or above k+m;
  * record ranges [rec_off, +32+shard_len) or non-empty out ranges [out_off,
  * +k*shard_len) not strictly ascending and disjoint in list order; a range

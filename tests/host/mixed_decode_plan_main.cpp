@@ -288,6 +288,67 @@ void test_rounds_beside_a_group_without_launch() {
     CHECK(moved == 3);
 }
 
+// The depth of the redo rounds, RS(5,4) with data shard 2 rotten and further
+// rotten parity shards: the launching rounds of each stripe on its own, with
+// and without verify_surplus, as literal figures (the ones the GPU tests'
+// Python model, tests/mixed_shapes.py settle, is held to in
+// tests/test_mixed_shapes.py and tests/test_gpu_mixed_decode.py); then all of
+// them in one batch beside clean stripes, which runs as deep as the deepest.
+void test_redo_depth() {
+    const int k = 5, m = 4;
+    const uint32_t all = 0x1ff, d2 = 1u << 2;
+    struct Row {
+        uint32_t parity;  // rotten parity shards (bits 5..8)
+        int off, on;      // launching rounds without / with verify_surplus
+        bool ok_off, ok_on;
+        uint32_t end_off, end_on;  // the final masks
+    };
+    const Row rows[] = {
+        {0x000, 2, 2, true, true, all & ~d2, all & ~d2},
+        {0x020, 3, 3, true, true, all & ~d2 & ~0x020u, all & ~d2 & ~0x020u},
+        {0x060, 4, 3, true, true, all & ~d2 & ~0x060u, all & ~d2 & ~0x060u},
+        {0x0e0, 5, 3, true, true, all & ~d2 & ~0x0e0u, all & ~d2 & ~0x0e0u},
+        {0x1e0, 5, 2, false, false, 0x01b, 0x01b},
+        {0x1c0, 2, 3, true, true, all & ~d2, all & ~d2 & ~0x1c0u},  // without verify_surplus parity 6 onwards is never read
+        {0x040, 2, 3, true, true, all & ~d2, all & ~d2 & ~0x040u},
+    };
+    const size_t nrows = sizeof(rows) / sizeof(rows[0]);
+    for (int vs = 0; vs < 2; ++vs) {
+        auto plan = [&](uint32_t mask, MaskPlan& p) { return plan_mask(k, m, mask, vs != 0, p); };
+        int deepest = 0;
+        for (const Row& r : rows) {
+            const std::vector<RecordDesc> d = make(k, {513}, {all});
+            const uint32_t rotten = d2 | r.parity;
+            uint32_t mask = all;
+            int launching = 0;
+            const int rounds = rounds_check::run_rounds(k, m, get_out_rule(k), d, &rotten, &mask, plan, &launching);
+            const bool ok = vs ? r.ok_on : r.ok_off;
+            CHECK(launching == (vs ? r.on : r.off));
+            CHECK(rounds == launching + (ok ? 0 : 1));  // the round that finds no plan launches nothing
+            CHECK(mask == (vs ? r.end_on : r.end_off) && (popcount32(mask) >= k) == ok);
+            deepest = std::max(deepest, launching);
+        }
+        CHECK(deepest == (vs ? 3 : 5));
+        // one batch: every row between clean stripes, lengths mixed
+        std::vector<uint32_t> rotten, masks, lens;
+        for (size_t i = 0; i < nrows; ++i) {
+            rotten.push_back(d2 | rows[i].parity);
+            rotten.push_back(0);
+            lens.push_back((uint32_t)(i % 2 ? 1025 : 7));
+            lens.push_back(33);
+        }
+        masks.assign(rotten.size(), all);
+        const std::vector<RecordDesc> d = make(k, lens, {all});
+        int launching = 0;
+        rounds_check::run_rounds(k, m, get_out_rule(k), d, rotten.data(), masks.data(), plan, &launching);
+        CHECK(launching == deepest);
+        for (size_t i = 0; i < nrows; ++i) {
+            CHECK(masks[2 * i] == (vs ? rows[i].end_on : rows[i].end_off));
+            CHECK(masks[2 * i + 1] == all);
+        }
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -297,6 +358,7 @@ int main() {
     test_split();
     test_redo();
     test_rounds_beside_a_group_without_launch();
+    test_redo_depth();
     printf("mixed decode plan ok\n");
     return 0;
 }

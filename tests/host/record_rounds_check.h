@@ -47,10 +47,13 @@ uint32_t settle(uint32_t mask, uint32_t rotten, PlanFn plan) {
 //     the shards of read_mask() once each;
 //   - redo is ascending, every redone stripe lost a bit, no mask gained one, and
 //     a stripe without a launch is neither redone nor changed.
-// At the end every mask is what settle() says.
+// At the end every mask is what settle() says.  *launching (optional): the
+// rounds that had a launch, which is what record_rounds runs; the count
+// returned is one higher when the last stripes end without a plan, in a round
+// that only finds that out.
 template <class PlanFn>
 int run_rounds(int k, int m, const OutRule& rule, const std::vector<RecordDesc>& d, const uint32_t* rotten,
-               uint32_t* masks, PlanFn plan) {
+               uint32_t* masks, PlanFn plan, int* launching = nullptr) {
     const size_t n = d.size(), t = (size_t)(k + m);
     std::vector<uint32_t> want(n);
     for (size_t s = 0; s < n; ++s) want[s] = settle(masks[s], rotten[s], plan);
@@ -105,6 +108,7 @@ int run_rounds(int k, int m, const OutRule& rule, const std::vector<RecordDesc>&
             CHECK(rows_read == p.read_mask() && unread == p.written.size());
         }
         CHECK(li == r.launches.size() && at == r.table.size() && tabled == launched);
+        if (launching && !r.launches.empty()) ++*launching;
         // the fake kernel: of every launch, every stripe of its slice, every row read
         std::vector<uint8_t> rows(n * t, 0xaa);
         for (const RoundLaunch& l : r.launches)

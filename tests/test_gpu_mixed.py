@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from mixed_shapes import SMALL_PERM, sweep_params
 
 pytestmark = pytest.mark.gpu
 
@@ -152,6 +153,15 @@ def test_lengths_and_geometries(gpu, oracle, k, m, order):
     lens = ordered(LENGTHS, order)
     assert sorted(lens) == sorted(LENGTHS)
     check_dev(Batch(oracle, k, m, lens, seed=len(order)))
+
+
+@pytest.mark.parametrize("k,m", sweep_params(1))
+def test_every_shape(gpu, oracle, k, m):
+    """Every instantiation of the kernel, k = 1..16 by m = 1..4, over the
+    small length set (mixed_shapes.py): HH256S, the guard layout of
+    test_lengths_and_geometries, whole arenas compared
+    (test_mixed_shapes.py: the parameters are all 64 built shapes)."""
+    check_dev(Batch(oracle, k, m, SMALL_PERM, seed=m), algos=(HH,))
 
 
 # -- 3 -----------------------------------------------------------------------------

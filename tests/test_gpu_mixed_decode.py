@@ -9,6 +9,8 @@ import shutil
 import numpy as np
 import pytest
 
+from mixed_shapes import SMALL_PERM, get_cases, sweep_params, plan_get, popcount, settle
+
 pytestmark = pytest.mark.gpu
 
 FILL = 0xA5
@@ -108,8 +110,10 @@ class Recs:
         """lost[j]: the data shards of stripe j that must have been rebuilt
         (default: those absent); failed: {stripe: status}.  Rebuilt windows
         hold the original data, served bits are the rest, and every other
-        byte of out holds FILL (the windows of a failed stripe's absent data
-        shards are unspecified)."""
+        byte of out holds FILL.  The windows of a failed stripe's absent data
+        shards are unspecified, and so are those of the data shards lost[j]
+        names for it: the ones the case made rotten, which count as absent
+        from the round that finds them and are written before the verdict."""
         status, served, out = res
         failed = failed or {}
         k = self.k
@@ -120,7 +124,7 @@ class Recs:
             o0 = self.out_off[j]
             if j in failed:
                 for c in range(k):
-                    if c in self.absent[j] or c in self.null:
+                    if c in self.absent[j] or c in self.null or c in lost.get(j, ()):
                         skip[o0 + c * S:o0 + (c + 1) * S] = True
                 continue
             gone = set(lost.get(j, [c for c in range(k) if c in self.absent[j] or c in self.null]))
@@ -178,6 +182,26 @@ def test_lengths(gpu, oracle, k, m, kind):
         for algo in ((HH, LEGACY) if (k, m) == (4, 2) else (HH,)):
             b = Recs(oracle, k, m, lens, algo, absent=[gone] * len(lens))
             b.check(b.run_dev(), {})
+
+
+@pytest.mark.parametrize("C,R", sweep_params(0))
+def test_every_shape(gpu, oracle, C, R):
+    """Instantiation <C, R> of the kernel, every one of them, over the small
+    length set (mixed_shapes.py): (C, 0, 0) with all present, and every
+    (C, R, e) as geometry (C, R) with e data shards absent in every stripe and
+    verify_surplus on, once the lowest e (sources are not the data prefix) and
+    once the highest e (lost[] takes large values).  Rebuilt windows hold the
+    data, served bits are right, every other byte of out holds FILL, the
+    arenas are unchanged.  The union over the parameters is every
+    reachable shape (test_mixed_shapes.py)."""
+    for k, m, absent, shape in get_cases(C, R):
+        plan = plan_get(k, m, (1 << (k + m)) - 1 & ~bits(absent), True)
+        assert (k, len(plan[1]) + len(plan[2]), len(plan[1])) == shape, (k, m, absent)
+        b = Recs(oracle, k, m, SMALL_PERM, absent=[absent] * len(SMALL_PERM), seed=m)
+        try:
+            b.check(b.run_dev(), {})
+        except AssertionError as err:
+            raise AssertionError(f"shape {shape}, RS({k},{m}), absent {absent}: {err}") from err
 
 
 def test_null_arena_is_absent_whatever_present_says(gpu, oracle):
@@ -244,6 +268,161 @@ def test_rot_found_during_the_read(gpu, oracle, k, m):
     for j, shard, at in rots:
         b.flip(j, shard, at)
     b.check(b.run_dev(), lost)
+
+
+# -- 5b: redo cascades ---------------------------------------------------------------
+#
+# More than two rounds: state that lives on the device across rounds (the
+# mismatch words, the flags by kernel row, the table region, out windows
+# written from a source that later proves rotten).  The round count is not
+# observable through the ABI; what is expected of each stripe comes from the
+# planner rule restated in mixed_shapes.settle, whose round counts are asserted
+# here against literal figures, so a case that stops reaching the depth it was
+# written for fails.
+
+class Cascade:
+    """Stripes of lengths 7, 33, 513 and 1025 for every case (absent, rotten,
+    rewritten), each followed by a clean neighbour of the same length: the
+    shards of `rotten` get one byte flipped (header and body in turn),
+    those of `rewritten` a valid digest over a wrong body.  From the model:
+    the final masks, the rounds, lost[j] (the data shards outside the final
+    mask) and failed (TOO_FEW: fewer than k left; INCONSISTENT: a rewritten
+    record among the last plan's surplus)."""
+
+    def __init__(self, O, k, m, cases, verify_surplus, lens=(7, 33, 513, 1025)):
+        specs = []
+        for S in lens:
+            for case in cases:
+                specs += [(S,) + tuple(case), (S, (), (), ())]
+        self.b = Recs(O, k, m, [s[0] for s in specs], absent=[s[1] for s in specs], seed=k)
+        self.vs, self.lost, self.failed, self.rounds, self.final, self.shapes = verify_surplus, {}, {}, [], [], []
+        for j, (S, absent, rotten, rewritten) in enumerate(specs):
+            for i, shard in enumerate(rotten):
+                self.b.flip(j, shard, (S - 1, -5, S // 2, -32)[(j // 2 + i) % 4])
+            for shard in rewritten:
+                self.b.rewrite(j, shard)
+            final, rounds, shapes = settle(k, m, (1 << (k + m)) - 1 & ~bits(absent), bits(rotten), verify_surplus)
+            self.final.append(final)
+            self.rounds.append(rounds)
+            self.shapes.append(shapes)
+            self.lost[j] = [c for c in range(k) if not final >> c & 1]
+            if popcount(final) < k:
+                self.failed[j] = TOO_FEW
+            else:
+                src, _, surplus = plan_get(k, m, final, verify_surplus)
+                assert not set(rewritten) & set(src)  # a wrong body under a valid digest is only ever compared
+                if set(rewritten) & set(surplus):
+                    self.failed[j] = INCONSISTENT
+        self.per_case = len(cases)
+
+    def of_case(self, values):
+        """values of the rotten stripes, per case (the same for every length)."""
+        rows = [values[a:a + 2 * self.per_case:2] for a in range(0, len(values), 2 * self.per_case)]
+        assert all(r == rows[0] for r in rows)
+        return rows[0]
+
+    def status_of_case(self):
+        return self.of_case([self.failed.get(j, OK) for j in range(self.b.n)])
+
+    def check_dev(self):
+        res = self.b.run_dev(self.vs)
+        self.b.check(res, self.lost, self.failed)
+        return res
+
+
+def ladder_cases(k):
+    """Data shard 2 rotten (found in round 1, which reads the data shards
+    only) and the parity shards k+i of each set rotten; then data shard 2
+    absent from the start, which ends on the same masks one round sooner."""
+    sets = [(), (0,), (0, 1), (0, 1, 2), (0, 1, 2, 3), (1, 2, 3), (1,)]
+    cases = [((), (2,) + tuple(k + i for i in p), ()) for p in sets]
+    return cases + [((2,), (), ()), ((2,), (k,), ()), ((2,), (k, k + 1, k + 2), ())]
+
+
+# rounds of ladder_cases, m = 4, for any k >= 3 (those of RS(5,4) are CHECKed
+# against the shipped planner in tests/host/mixed_decode_plan_main.cpp); the
+# fifth case ends with k - 1 shards
+LADDER_ROUNDS = {False: [2, 3, 4, 5, 5, 2, 2, 1, 2, 4], True: [2, 3, 3, 3, 2, 3, 3, 1, 2, 2]}
+LADDER_STATUS = [OK, OK, OK, OK, TOO_FEW, OK, OK, OK, OK, OK]
+
+
+def ladder(O, k, verify_surplus):
+    c = Cascade(O, k, 4, ladder_cases(k), verify_surplus)
+    assert c.of_case(c.rounds) == LADDER_ROUNDS[verify_surplus]
+    assert c.status_of_case() == LADDER_STATUS
+    assert c.rounds[1::2] == [1] * (c.b.n // 2)  # the clean neighbours
+    final = c.of_case(c.final)
+    assert final[1] == final[8] and c.of_case(c.rounds)[1] > c.of_case(c.rounds)[8]  # one mask, reached in different rounds
+    if not verify_surplus:
+        assert c.of_case(c.shapes)[3][1:] == [(k, 1, 1)] * 4
+        assert final[5] == (1 << (k + 4)) - 1 & ~(1 << 2)  # parity k+1 onwards is never read
+    else:
+        assert c.of_case(c.shapes)[1][1:] == [(k, 4, 1), (k, 3, 1)]
+        assert final[5] == bits(range(k + 1)) & ~(1 << 2)  # a rotten surplus leaves the mask too
+    return c
+
+
+@pytest.mark.parametrize("verify_surplus", [False, True])
+@pytest.mark.parametrize("k", [5, 8])
+def test_redo_ladder(gpu, oracle, k, verify_surplus):
+    """Stripes that need one to five rounds in one batch, each beside a clean
+    neighbour of its workgroup: every stripe RSG_OK with the data in the
+    rebuilt window (written in an early round from a source that later proved
+    rotten, and again) except the one left with k - 1 shards; all other out
+    bytes FILL."""
+    ladder(oracle, k, verify_surplus).check_dev()
+
+
+@pytest.mark.parametrize("verify_surplus", [False, True])
+def test_redo_ladder_host_form(gpu, oracle, verify_surplus):
+    """The RS(5,4) ladder through rsg_decode_mixed_host (one sub-batch): the
+    device form's statuses, served bits and bytes; the copy-back goes by the
+    final masks, so h_out is untouched outside the rebuilt windows of good
+    stripes, the failed stripe's windows included."""
+    from rustfs_amd import Erasure
+    c = ladder(oracle, 5, verify_surplus)
+    b = c.b
+    files = [f.copy() for f in b.files]
+    out = np.full(b.out_len, FILL, dtype=np.uint8)
+    status, served = Erasure(5, 4, 1 << 20).decode_mixed_host(files, b.desc(), out, verify_surplus)
+    for i in range(b.t):
+        assert np.array_equal(files[i], b.files[i]), f"arena {i} changed"
+    b.check((status, served, out), c.lost, c.failed)
+    dev = c.check_dev()
+    assert dev[0] == status
+    same = np.ones(b.out_len, dtype=bool)
+    for j in c.failed:
+        o0, S = b.out_off[j], b.lens[j]
+        assert (out[o0:o0 + b.k * S] == FILL).all(), f"h_out of failed stripe {j} written"
+        same[o0:o0 + b.k * S] = False  # the device form's windows of a failed stripe are unspecified
+    assert [s for j, s in enumerate(served) if j not in c.failed] == [s for j, s in enumerate(dev[1]) if j not in c.failed]
+    assert np.array_equal(out[same], dev[2][same])
+
+
+def test_mismatch_word_across_rounds(gpu, oracle):
+    """A stripe's mismatch word is set in one round and must not decide a
+    later one.  RS(4,2): (a) data 0 absent, surplus parity 5 flipped: round 1
+    compares good sources with a rotten surplus, round 2 is (4,1,1) with no
+    compared row, RSG_OK; (b) the same plus source parity 4 flipped: TOO_FEW,
+    not INCONSISTENT.  RS(5,3): (c) data 2 flipped and surplus 6 rewritten
+    (valid digest, wrong body): INCONSISTENT, from round 2 (the rewritten
+    record verifies, so the model gives two rounds); (c') data 2 and source
+    parity 5 flipped, surplus 7 rewritten: round 2 compares against garbage,
+    round 3 finds the real mismatch, INCONSISTENT after three rounds; (d) data
+    0 absent and source parity 5 flipped: round 1 computed from garbage, set
+    the word and wrote the window, round 2 leaves RSG_OK and the data."""
+    a = Cascade(oracle, 4, 2, [((0,), (5,), ()), ((0,), (4, 5), ())], True)
+    assert a.of_case(a.rounds) == [2, 1] and a.status_of_case() == [OK, TOO_FEW]
+    assert a.of_case(a.shapes)[0] == [(4, 2, 1), (4, 1, 1)]
+    a.check_dev()
+    c = Cascade(oracle, 5, 3, [((), (2,), (6,)), ((), (2, 5), (7,)), ((0,), (5,), ())], True)
+    assert c.of_case(c.rounds) == [2, 3, 2] and c.status_of_case() == [INCONSISTENT, INCONSISTENT, OK]
+    assert c.of_case(c.shapes) == [[(5, 0, 0), (5, 3, 1)], [(5, 0, 0), (5, 3, 1), (5, 2, 1)], [(5, 3, 1), (5, 2, 1)]]
+    c.check_dev()
+    # without verify_surplus nothing is compared: the rewritten records are never read
+    d = Cascade(oracle, 5, 3, [((), (2,), (6,)), ((), (2, 5), (7,)), ((0,), (5,), ())], False)
+    assert d.of_case(d.rounds) == [2, 3, 2] and d.status_of_case() == [OK, OK, OK]
+    d.check_dev()
 
 
 # -- 6 -----------------------------------------------------------------------------

@@ -13,6 +13,8 @@ import shutil
 import numpy as np
 import pytest
 
+from mixed_shapes import SMALL_PERM, heal_cases, sweep_params, plan_heal, settle_heal
+
 pytestmark = pytest.mark.gpu
 
 FILL = 0xA5
@@ -203,6 +205,26 @@ def test_lengths(gpu, oracle, k, m, kind):
             b.check(b.run_dev())
 
 
+@pytest.mark.parametrize("C,R", sweep_params(1))
+def test_every_shape(gpu, oracle, C, R):
+    """Instantiation <C, R> of the kernel, every one of them, over the small
+    length set (mixed_shapes.py): every (C, R, e) as geometry (C, R) with e
+    targets and every other shard present, once the lowest e shard indices
+    (data first) with the target records packed back to back, so that a
+    spilled store lands in the neighbour's header, and once the highest e
+    (parity) at odd offsets between guard bytes.  Whole target arenas
+    compared, source arenas unchanged.  The union over the parameters is all
+    160 shapes (test_mixed_shapes.py)."""
+    for k, m, targets, dense, shape in heal_cases(C, R):
+        plan = plan_heal(k, m, (1 << (k + m)) - 1, bits(targets))
+        assert (k, len(plan[1]) + len(plan[2]), len(plan[1])) == shape, (k, m, targets)
+        b = Heal(oracle, k, m, SMALL_PERM, targets, dense=dense, seed=m)
+        try:
+            b.check(b.run_dev())
+        except AssertionError as err:
+            raise AssertionError(f"shape {shape}, RS({k},{m}), targets {targets}: {err}") from err
+
+
 @pytest.mark.parametrize("k,m", [(2, 2), (4, 2), (5, 3), (8, 4), (16, 4)])
 def test_densely_packed_targets(gpu, oracle, k, m):
     """Target records back to back: a store that spills over a record's end
@@ -307,6 +329,13 @@ def test_rot_found_during_the_read(gpu, oracle, k, m):
         b.flip(j, shard, at)
     for j, shard in rew:
         b.rewrite(j, shard)
+    # the planner rule (mixed_shapes.py): a heal reads every readable non-target
+    # shard in its first round, so none of these stripes launches more than twice
+    for j in range(b.n):
+        rotten = bits(s for jj, s, _ in rots if jj == j)
+        final, rounds, _ = settle_heal(k, m, bits(range(k + m)), bits((0,)), rotten)
+        assert rounds <= 2 and (rounds == 2) == (bool(rotten) and failed.get(j) != TOO_FEW)
+        assert (bin(final).count("1") < k) == (failed.get(j) == TOO_FEW)
     b.check(b.run_dev(), failed)
     # the same rot, two targets (a data and a parity shard), dense records
     b2 = Heal(oracle, k, m, lens, targets=(0, k + m - 1), dense=True)
