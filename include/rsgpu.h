@@ -588,6 +588,46 @@ int rsg_bitrot_verify_mixed_dev(rsg_ctx *ctx, int algo, int n_arenas, const uint
 int rsg_bitrot_verify_mixed_host(rsg_ctx *ctx, int algo, int n_arenas, const uint8_t *const *h_arenas,
                                  size_t n, const rsg_file_desc *h_desc, int *h_status);
 
+/* ---- gathered block encode: n unrelated blocks in one launch pair ----
+ *
+ * The reference calls ReedSolomonEncoder::encode once per 1 MiB block
+ * (erasure.rs:396-408, from encode.rs:504-530) and BitrotWriter::write hashes
+ * each of the k+m shards (bitrot.rs:496-502).  rsg_encode_blocks takes n such
+ * blocks, each as the k+m host pointers rsg_encode takes, of any alignment
+ * and with its own shard_len (1 .. 0xffffffff), writes every block's parity
+ * and, with algo HIGHWAY256S or LEGACY, the (k+m)*32 digest bytes of every
+ * block whose `digests` is not NULL (algo NONE ignores the pointers).
+ * Synchronous.
+ *
+ * Validation is all or nothing, before anything is written: a NULL pointer,
+ * a shard_len above 0xffffffff, or a parity or digest range that meets any
+ * other shard or digest range of the call is RSG_ERR_INVALID_ARG; shard_len 0
+ * is RSG_ERR_EMPTY_SHARD; geometry errors are rsg_encode's.  Data ranges may
+ * overlap each other.  n == 0 is RSG_OK.
+ *
+ * For k <= 16, m <= 4 consecutive blocks are taken into sub-batches that fit
+ * RSG_BLOCKS_STAGE_BYTES of staging, each one encode launch and, with
+ * digests, one hash launch.  Shards in page-locked memory the device can
+ * address are read, and their parity written, in place (RSG_ZERO_COPY=0:
+ * staged like pageable ones); pageable shards are staged, contiguous runs
+ * with one copy.  Exactly the bytes [shard, shard + shard_len) of a parity
+ * shard and the (k+m)*32 digest bytes are written.  A block larger than the
+ * stage, and every other geometry, goes block by block through rsg_encode's
+ * path (and rsg_hash's digest launch): the same bytes.
+ *
+ * rsg_encode_hashed: rsg_encode plus the digest of every shard (the
+ * BitrotWriter prefix), one block per call: the seam a caller uses to skip
+ * the writer's own hash.  digests must not be NULL; algo NONE writes none. */
+#define RSG_BLOCKS_STAGE_BYTES (32u << 20)
+typedef struct rsg_block {
+    uint8_t *const *shards; /* k+m host pointers, k data then m parity, as rsg_encode's */
+    uint64_t shard_len;
+    uint8_t *digests;       /* (k+m)*32 bytes in shard order, or NULL */
+} rsg_block;
+int rsg_encode_blocks(rsg_ctx *ctx, int k, int m, size_t n, const rsg_block *blocks, int algo);
+int rsg_encode_hashed(rsg_ctx *ctx, int k, int m, size_t shard_len, uint8_t *const *shards,
+                      uint8_t *digests, int algo);
+
 /* Page-lock / release host memory for DMA (hipHostRegister). */
 int rsg_pin(void *ptr, size_t bytes);
 int rsg_unpin(void *ptr);

@@ -67,10 +67,22 @@ EXPORTED = (
     "rsg_encode_mixed_dev", "rsg_encode_mixed_host", "rsg_encode_mixed_host_submit",
     "rsg_decode_mixed_dev", "rsg_decode_mixed_host", "rsg_heal_mixed_dev", "rsg_heal_mixed_host",
     "rsg_bitrot_verify_mixed_dev", "rsg_bitrot_verify_mixed_host",
+    "rsg_encode_blocks", "rsg_encode_hashed",
 )
 
 # Staging bytes per sub-batch of rsg_encode_mixed_host (include/rsgpu.h)
 RSG_MIXED_STAGE_BYTES = 32 << 20
+# Staging bytes per sub-batch of rsg_encode_blocks (include/rsgpu.h)
+RSG_BLOCKS_STAGE_BYTES = 32 << 20
+
+
+class rsg_block(ctypes.Structure):
+    """rsg_block (include/rsgpu.h): one block of rsg_encode_blocks."""
+    _fields_ = [("shards", ctypes.POINTER(ctypes.c_void_p)),  # k+m host pointers, k data then m parity
+                ("shard_len", ctypes.c_uint64),
+                ("digests", ctypes.c_void_p)]                 # (k+m)*32 bytes, or NULL
+
+
 # rsg_stripe_desc (include/rsgpu.h): three little-endian u64 per stripe; a
 # numpy (n, 3) uint64 array [data_off, parity_off, shard_len] has its layout
 STRIPE_DESC_FIELDS = 3
@@ -167,6 +179,8 @@ def load():
         L.rsg_heal_mixed_host.argtypes = [P, I, I, S, P, P, P, I, P]
         L.rsg_bitrot_verify_mixed_dev.argtypes = [P, I, I, P, S, P, P, P]
         L.rsg_bitrot_verify_mixed_host.argtypes = [P, I, I, P, S, P, P]
+        L.rsg_encode_blocks.argtypes = [P, I, I, S, P, I]
+        L.rsg_encode_hashed.argtypes = [P, I, I, S, P, P, I]
         _lib = L
         return L
 

@@ -19,11 +19,13 @@
 #include <map>
 #include <memory>
 #include <atomic>
+#include <condition_variable>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/rsgpu.h"
+#include "rs_blocks.h"
 #include "rs_kernels.h"
 #include "rs_mixed.h"
 
@@ -567,9 +569,29 @@ struct RecScratch {
     }
 };
 
+// One batch of the gathered block encode in flight (rsg_encode_blocks,
+// rsg_encode_hashed): a stream, the device staging buffer with the tables behind
+// it, and the page-locked buffer the tables go up from and the staged digests
+// come back to.
+struct BlockSlot {
+    hipStream_t stream = nullptr;
+    uint8_t* d = nullptr;  // RSG_BLOCKS_STAGE_BYTES of stage, then kBlockTableBytes of tables
+    uint8_t* h = nullptr;  // kBlockTableBytes of tables, then kBlockDigestBytes of digests
+    bool busy = false;
+};
+constexpr size_t kBlockTableBytes = (size_t)rsg::blocks::table_bytes_max(rsg::blocks::kMaxC, rsg::blocks::kMaxR);
+constexpr size_t kBlockDigestBytes = rsg::blocks::kMaxBatchBlocks * (size_t)(rsg::blocks::kMaxC + rsg::blocks::kMaxR) * 32;
+
+constexpr int kBlockSlots = 4;  // batches in flight: a process has 4 hardware queues
+
 struct rsg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+
+    // gathered block encode: as many slots as batches may be in flight
+    std::mutex blk_mu;
+    std::condition_variable blk_cv;
+    BlockSlot blk_slots[kBlockSlots];
 
     // record-engine scratch pool (RecScratch): taken per call, returned when
     // the call's ticket finishes
@@ -876,6 +898,14 @@ void rsg_destroy(rsg_ctx* ctx) {
             (void)hipStreamDestroy(l.stream);
         }
         if (l.d_buf) (void)hipFree(l.d_buf);
+    }
+    for (BlockSlot& b : ctx->blk_slots) {
+        if (b.stream) {
+            (void)hipStreamSynchronize(b.stream);
+            (void)hipStreamDestroy(b.stream);
+        }
+        if (b.d) (void)hipFree(b.d);
+        if (b.h) (void)hipHostFree(b.h);
     }
     for (int i = 0; i < rsg_ctx::kPipeSlots; ++i) {
         if (ctx->pipe_stream[i]) {
@@ -3202,7 +3232,12 @@ int rsg_bitrot_verify_dev(rsg_ctx* ctx, int algo, size_t n_files, const uint8_t*
 
 // ---- host-buffer API ----
 
-int rsg_encode(rsg_ctx* ctx, int k, int m, size_t shard_len, uint8_t* const* shards) {
+}  // extern "C"
+
+namespace {
+
+// rsg_encode: one block on a host lane (also the per-block path of rsg_encode_blocks).
+int encode_one(rsg_ctx* ctx, int k, int m, size_t shard_len, uint8_t* const* shards) {
     int st = enter(ctx);
     if (st) return st;
     if ((st = check_geometry(k, m))) return st;
@@ -3252,6 +3287,186 @@ int rsg_encode(rsg_ctx* ctx, int k, int m, size_t shard_len, uint8_t* const* sha
                 return st;
     }
     return hip_status(hipStreamSynchronize(s));
+}
+
+// ---- gathered block encode (rs_blocks_plan.h, rs_blocks.hip) ----
+
+namespace bk = rsg::blocks;
+
+static_assert(sizeof(rsg_block) == sizeof(bk::Block) && offsetof(rsg_block, shard_len) == offsetof(bk::Block, shard_len) &&
+                  offsetof(rsg_block, digests) == offsetof(bk::Block, digests),
+              "rsg_block is the planner's Block");
+
+int blocks_verdict_status(bk::Verdict v) {
+    return v == bk::kOk ? RSG_OK : v == bk::kEmpty ? RSG_ERR_EMPTY_SHARD : RSG_ERR_INVALID_ARG;
+}
+
+// A free slot, marked busy and with its buffers made; null with *st set on an
+// allocation error.
+BlockSlot* take_block_slot(rsg_ctx* ctx, int* st) {
+    BlockSlot* b = nullptr;
+    {
+        std::unique_lock<std::mutex> g(ctx->blk_mu);
+        for (;;) {
+            for (BlockSlot& c : ctx->blk_slots)
+                if (!c.busy && !b) b = &c;
+            if (b) break;
+            ctx->blk_cv.wait(g);
+        }
+        b->busy = true;
+    }
+    hipError_t e = hipSuccess;
+    if (!b->stream) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (e == hipSuccess && !b->d) e = hipMalloc((void**)&b->d, (size_t)RSG_BLOCKS_STAGE_BYTES + kBlockTableBytes);
+    if (e == hipSuccess && !b->h) e = hipHostMalloc((void**)&b->h, kBlockTableBytes + kBlockDigestBytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        *st = hip_status(e);
+        std::lock_guard<std::mutex> g(ctx->blk_mu);
+        b->busy = false;
+        ctx->blk_cv.notify_one();
+        return nullptr;
+    }
+    return b;
+}
+
+void give_block_slot(rsg_ctx* ctx, BlockSlot* b) {
+    {
+        std::lock_guard<std::mutex> g(ctx->blk_mu);
+        b->busy = false;
+    }
+    ctx->blk_cv.notify_one();
+}
+
+// One sub-batch that fits the stage: the plan's copies and launches on a
+// slot's stream, then the wait.
+int run_block_batch(rsg_ctx* ctx, const Codec& cd, const bk::Block* b, size_t n, int algo) {
+    const int k = cd.k, m = cd.m, t = k + m;
+    const bool want = algo != RSG_HASH_NONE;
+    // the device's view of every shard and digest buffer it can address:
+    // one lookup per run of shards that are contiguous in host memory
+    std::vector<uint64_t> view(n * (size_t)t, 0), dview(n, 0);
+    if (zero_copy_enabled()) {
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t len = b[i].shard_len;
+            for (int s0 = 0; s0 < t;) {
+                int s1 = s0 + 1;
+                while (s1 < t && b[i].shards[s1] == b[i].shards[s1 - 1] + len) ++s1;
+                if (const uint8_t* dv = pinned_view(b[i].shards[s0], (size_t)(len * (uint64_t)(s1 - s0)), ctx->device))
+                    for (int s = s0; s < s1; ++s) view[i * (size_t)t + s] = (uint64_t)(uintptr_t)(dv + (uint64_t)(s - s0) * len);
+                s0 = s1;
+            }
+            if (want && b[i].digests)
+                dview[i] = (uint64_t)(uintptr_t)pinned_view(b[i].digests, (size_t)t * 32, ctx->device);
+        }
+    }
+    int st = RSG_OK;
+    BlockSlot* slot = take_block_slot(ctx, &st);
+    if (!slot) return st;
+    bk::BatchPlan p;
+    bk::plan_batch(k, m, n, b, want, view.data(), dview.data(), (uint64_t)(uintptr_t)slot->d, p);
+    const bk::TableLayout lay = bk::table_layout(p);
+    hipStream_t s = slot->stream;
+    if (p.stage_bytes > RSG_BLOCKS_STAGE_BYTES || lay.bytes > kBlockTableBytes) st = RSG_ERR_INVALID_ARG;  // split() keeps both
+    if (!st) {
+        std::memcpy(slot->h + lay.desc_off, p.desc.data(), p.desc.size() * sizeof(bk::BlockDesc));
+        std::memcpy(slot->h + lay.tile_off, p.tile0.data(), p.tile0.size() * sizeof(uint32_t));
+        if (!p.unit.empty()) std::memcpy(slot->h + lay.unit_off, p.unit.data(), p.unit.size() * sizeof(bk::HashUnit));
+        uint8_t* d_tab = slot->d + RSG_BLOCKS_STAGE_BYTES;
+        st = hip_status(hipMemcpyAsync(d_tab, slot->h, (size_t)lay.bytes, hipMemcpyHostToDevice, s));
+        for (size_t c = 0; c < p.up.size() && !st; ++c)
+            st = hip_status(hipMemcpyAsync((void*)(uintptr_t)p.up[c].dev, p.up[c].host, (size_t)p.up[c].bytes,
+                                           hipMemcpyHostToDevice, s));
+        if (!st) {
+            rsg::EncodeBlocksParams e;
+            e.desc = (const bk::BlockDesc*)(d_tab + lay.desc_off);
+            e.tile0 = (const uint32_t*)(d_tab + lay.tile_off);
+            e.n = (uint32_t)n;
+            std::memset(e.tab, 0, sizeof(e.tab));
+            for (int r = 0; r < m; ++r)
+                for (int c = 0; c < k; ++c) coef_tables(cd.matrix[(size_t)(k + r) * k + c], e.tab[r][c]);
+            st = hip_status(rsg::launch_encode_blocks(e, k, m, p.tile0[n], s));
+        }
+        if (!st && !p.unit.empty()) {
+            rsg::HashBlocksParams h;
+            h.unit = (const bk::HashUnit*)(d_tab + lay.unit_off);
+            h.n = p.unit.size();
+            std::memcpy(h.key, hash_key(algo), sizeof(h.key));
+            st = hip_status(rsg::launch_hash_blocks(h, s));
+        }
+        for (size_t c = 0; c < p.down.size() && !st; ++c)
+            st = hip_status(hipMemcpyAsync(p.down[c].host, (const void*)(uintptr_t)p.down[c].dev, (size_t)p.down[c].bytes,
+                                           hipMemcpyDeviceToHost, s));
+        uint8_t* h_dig = slot->h + kBlockTableBytes;
+        if (!st && p.digest_bytes)
+            st = hip_status(hipMemcpyAsync(h_dig, (const void*)(uintptr_t)p.digest_dev, (size_t)p.digest_bytes,
+                                           hipMemcpyDeviceToHost, s));
+        // nothing queued may outlive the call, whatever failed
+        const int sst = hip_status(hipStreamSynchronize(s));
+        if (!st) st = sst;
+        if (!st)
+            for (const bk::DigestMove& mv : p.moves) std::memcpy(mv.host, h_dig + mv.off, (size_t)t * 32);
+    }
+    give_block_slot(ctx, slot);
+    return st;
+}
+
+// One block through the per-block path: rsg_encode's, then rsg_hash's digest
+// launch per shard.
+int run_block_alone(rsg_ctx* ctx, int k, int m, const bk::Block& b, int algo) {
+    int st = encode_one(ctx, k, m, (size_t)b.shard_len, b.shards);
+    if (algo != RSG_HASH_NONE && b.digests)
+        for (int s = 0; s < k + m && !st; ++s)
+            st = rsg_hash(ctx, algo, b.shards[s], (size_t)b.shard_len, b.digests + 32 * (size_t)s);
+    return st;
+}
+
+// Validated blocks of a valid geometry (m > 0), in sub-batches.
+int run_blocks(rsg_ctx* ctx, int k, int m, size_t n, const bk::Block* b, int algo) {
+    int st = RSG_OK;
+    if (!bk::kernel_geometry(k, m)) {
+        for (size_t i = 0; i < n && !st; ++i) st = run_block_alone(ctx, k, m, b[i], algo);
+        return st;
+    }
+    auto cd = get_codec(k, m);
+    if (!cd) return RSG_ERR_INVALID_ARG;
+    std::vector<bk::SubBatch> subs;
+    bk::split(k, m, n, b, algo != RSG_HASH_NONE, RSG_BLOCKS_STAGE_BYTES, subs);
+    for (const bk::SubBatch& sb : subs) {
+        st = sb.alone ? run_block_alone(ctx, k, m, b[sb.first], algo) : run_block_batch(ctx, *cd, b + sb.first, sb.count, algo);
+        if (st) break;
+    }
+    return st;
+}
+
+int encode_blocks_checked(rsg_ctx* ctx, int k, int m, size_t n, const bk::Block* b, int algo) {
+    int st = enter(ctx);
+    if (st) return st;
+    if ((st = check_geometry(k, m))) return st;
+    if (m == 0) return RSG_ERR_ZERO_PARITY_SHARDS;
+    if (algo != RSG_HASH_NONE && !hash_key(algo)) return RSG_ERR_INVALID_ARG;
+    if (n == 0) return RSG_OK;
+    if ((st = blocks_verdict_status(bk::validate(k, m, n, b, algo != RSG_HASH_NONE)))) return st;
+    return run_blocks(ctx, k, m, n, b, algo);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsg_encode(rsg_ctx* ctx, int k, int m, size_t shard_len, uint8_t* const* shards) {
+    return encode_one(ctx, k, m, shard_len, shards);
+}
+
+int rsg_encode_blocks(rsg_ctx* ctx, int k, int m, size_t n, const rsg_block* blocks, int algo) {
+    return encode_blocks_checked(ctx, k, m, n, (const bk::Block*)blocks, algo);
+}
+
+int rsg_encode_hashed(rsg_ctx* ctx, int k, int m, size_t shard_len, uint8_t* const* shards, uint8_t* digests, int algo) {
+    int st = enter(ctx);
+    if (st) return st;
+    if (!digests) return RSG_ERR_INVALID_ARG;
+    const bk::Block blk{shards, shard_len, digests};
+    return encode_blocks_checked(ctx, k, m, 1, &blk, algo);
 }
 
 int rsg_reconstruct(rsg_ctx* ctx, int k, int m, size_t shard_len, uint8_t* const* shards, const uint8_t* present,

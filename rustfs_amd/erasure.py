@@ -115,6 +115,22 @@ class ReedSolomonEncoder:
         check(_lib.load().rsg_encode(self._ctx().handle, self.data_shards, self.parity_shards, n, _ptrs(arrs)),
               "Reed-Solomon encode failed")
 
+    def encode_hashed(self, shards: List, algo: int = _lib.RSG_HASH_HIGHWAY256S) -> np.ndarray:
+        """encode plus the BitrotWriter digest of every shard (rsg_encode_hashed,
+        bitrot.rs:496-502): parity in place, returns the (k+m, 32) digests."""
+        if len(shards) != self.total:
+            raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT, "Reed-Solomon encode failed")
+        arrs = [_shard_view(s) for s in shards]
+        n = arrs[0].size
+        if any(a.size != n for a in arrs):
+            raise RsgError(_lib.RSG_ERR_INCONSISTENT_LENGTH, "Reed-Solomon encode failed")
+        for a in arrs[self.data_shards:]:
+            _writable(a)
+        digests = np.zeros((self.total, 32), dtype=np.uint8)
+        check(_lib.load().rsg_encode_hashed(self._ctx().handle, self.data_shards, self.parity_shards, n, _ptrs(arrs),
+                                            digests.ctypes.data, algo), "Reed-Solomon encode failed")
+        return digests
+
     def _reconstruct(self, shards: List, mode: int) -> None:
         if len(shards) != self.total:
             raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT,
@@ -402,6 +418,43 @@ class Erasure:
             ctx.handle, self.data_shards, self.parity_shards, S, n, stripes.ctypes.data, S, t * S, d,
             algo if d else _lib.RSG_HASH_NONE, ctypes.byref(tk)), "Reed-Solomon encode failed")
         return HostBatchTicket(ctx, tk.value, (stripes, digests))
+
+    # -- gathered blocks: n unrelated blocks of k+m shard buffers each (rsg_encode_blocks) --
+    def encode_blocks(self, blocks: Sequence[Sequence], digests: Optional[Sequence] = None,
+                      algo: int = _lib.RSG_HASH_HIGHWAY256S) -> None:
+        """Encode n unrelated blocks in one call (rsg_encode_blocks): blocks[i]
+        is a list of k+m uint8 buffers of one length (its own), k data then m
+        parity, anywhere in host memory and at any alignment; the parity
+        buffers are overwritten.  digests, if given, holds per block a
+        writable (k+m, 32) uint8 array or None (parity only for that block).
+        One launch pair per 32 MiB of staged shards for k <= 16, m <= 4."""
+        t = self.total_shard_count()
+        if digests is not None and len(digests) != len(blocks):
+            raise TypeError("digests must hold one entry (an array or None) per block")
+        n = len(blocks)
+        descs = (_lib.rsg_block * max(n, 1))()
+        keep = []
+        for i, shards in enumerate(blocks):
+            if len(shards) != t:
+                raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT, "Reed-Solomon encode failed")
+            arrs = [_shard_view(s) for s in shards]
+            if any(a.size != arrs[0].size for a in arrs):
+                raise RsgError(_lib.RSG_ERR_INCONSISTENT_LENGTH, "Reed-Solomon encode failed")
+            for a in arrs[self.data_shards:]:
+                _writable(a)
+            ptrs = _ptrs(arrs)
+            dg = digests[i] if digests is not None else None
+            if dg is not None:
+                dg = _writable(_shard_view(dg))
+                if dg.size != t * 32:
+                    raise TypeError("a block's digests must hold (k+m, 32) bytes")
+            keep.append((arrs, ptrs, dg))
+            descs[i].shards = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
+            descs[i].shard_len = arrs[0].size
+            descs[i].digests = dg.ctypes.data if dg is not None else None
+        check(_lib.load().rsg_encode_blocks(_lib.context(self._device).handle, self.data_shards, self.parity_shards, n,
+                                            ctypes.byref(descs), algo if digests is not None else _lib.RSG_HASH_NONE),
+              "Reed-Solomon encode failed")
 
     # -- mixed-length batches: every stripe its own shard length (rsg_encode_mixed_*) --
     def _mixed_desc(self, desc, data_len: int, parity_len: int, digests_len: Optional[int]) -> np.ndarray:
