@@ -628,6 +628,66 @@ int rsg_encode_blocks(rsg_ctx *ctx, int k, int m, size_t n, const rsg_block *blo
 int rsg_encode_hashed(rsg_ctx *ctx, int k, int m, size_t shard_len, uint8_t *const *shards,
                       uint8_t *digests, int algo);
 
+/* ---- gathered block reconstruct: n degraded blocks, verified, one launch ----
+ *
+ * The read half of the seam above.  The reference reads a block's shards
+ * through BitrotReader::read, which hashes each shard and fails on a mismatch
+ * (bitrot.rs:139-244), and hands the Option<Vec<u8>> list to
+ * ReedSolomonEncoder::reconstruct_data / reconstruct (erasure.rs:411-428,
+ * 897-933; heal.rs:186), once per block.  rsg_reconstruct_blocks takes n such
+ * blocks, each as rsg_reconstruct takes one (k+m writable shard_len buffers
+ * of any alignment and its own `present` bytes), with its own shard_len
+ * (1 .. 0xffffffff), and rebuilds them all in `mode` (one
+ * rsg_reconstruct_mode for the call), whatever the mix of loss patterns.
+ * Synchronous.
+ *
+ * Without verification (algo NONE, or a block's digests NULL) a block
+ * behaves exactly as rsg_reconstruct does on it.  With algo HIGHWAY256S or
+ * LEGACY and digests not NULL, every present shard of the block is hashed
+ * first; one whose digest differs from its 32-byte entry is treated as absent
+ * (as when BitrotReader::read fails), marked 1 in `bad` if that is given, and
+ * rebuilt in place if the mode rebuilds it (a rotten parity shard under
+ * RSG_RECONSTRUCT_DATA is only marked).  Entries of absent shards are
+ * ignored; the expected digests never leave the host.  The survivors are the
+ * first k usable shards in ascending order.
+ *
+ * status[i]: RSG_OK, or RSG_ERR_TOO_FEW_SHARDS when fewer than k shards of
+ * block i are usable after verification: none of that block's shard buffers
+ * is written, its `bad` is still filled, other blocks are unaffected.  The
+ * call returns RSG_OK when it ran to the end.  `bad`, where given, and status
+ * are always filled (zeros for a block that is not verified).
+ *
+ * Validation is all or nothing, before anything is written.
+ * RSG_ERR_INVALID_ARG: a NULL block list, shard list, shard pointer or
+ * `present`; shard_len above 0xffffffff; mode or algo out of range; status
+ * NULL while any block is verified; a shard or `bad` range that meets any
+ * other shard, `bad` or digest range of the call (digest ranges may meet each
+ * other).  shard_len 0 is RSG_ERR_EMPTY_SHARD; a block with fewer than k
+ * bytes set in `present` is RSG_ERR_TOO_FEW_SHARDS for the call; geometry
+ * errors are rsg_reconstruct's.  n == 0 is RSG_OK; m == 0 is RSG_OK with
+ * `bad` and status zeroed and nothing else written.
+ *
+ * For k <= 16, m <= 4 consecutive blocks are taken into sub-batches that fit
+ * RSG_BLOCKS_STAGE_BYTES of staging.  Without verification a sub-batch is one
+ * launch: shards in page-locked memory the device can address are read, and
+ * rebuilt, in place (RSG_ZERO_COPY=0: staged like pageable ones); pageable
+ * survivors are staged (only the k survivors, contiguous runs with one copy)
+ * and pageable targets copied back.  With verification every present shard
+ * is staged and crosses the link once; one hash launch, the digests back,
+ * then the one reconstruct launch.  Exactly the bytes
+ * [shard, shard + shard_len) of a rebuilt shard are written.  A block larger
+ * than the stage, and every other geometry, goes block by block through
+ * rsg_hash and rsg_reconstruct: the same bytes and outcomes. */
+typedef struct rsg_rblock {
+    uint8_t *const *shards; /* k+m host pointers, every one a writable shard_len buffer (as rsg_reconstruct) */
+    uint64_t shard_len;     /* 1 .. 0xffffffff */
+    const uint8_t *present; /* k+m bytes, != 0: the shard holds what was read */
+    const uint8_t *digests; /* expected (k+m)*32 bytes in shard order, or NULL; absent shards' entries ignored */
+    uint8_t *bad;           /* k+m bytes out or NULL: 1 where a present shard's digest did not match, else 0 */
+} rsg_rblock;
+int rsg_reconstruct_blocks(rsg_ctx *ctx, int k, int m, size_t n, const rsg_rblock *blocks,
+                           int mode, int algo, int *status /* n, may be NULL when algo is NONE */);
+
 /* Page-lock / release host memory for DMA (hipHostRegister). */
 int rsg_pin(void *ptr, size_t bytes);
 int rsg_unpin(void *ptr);

@@ -67,7 +67,7 @@ EXPORTED = (
     "rsg_encode_mixed_dev", "rsg_encode_mixed_host", "rsg_encode_mixed_host_submit",
     "rsg_decode_mixed_dev", "rsg_decode_mixed_host", "rsg_heal_mixed_dev", "rsg_heal_mixed_host",
     "rsg_bitrot_verify_mixed_dev", "rsg_bitrot_verify_mixed_host",
-    "rsg_encode_blocks", "rsg_encode_hashed",
+    "rsg_encode_blocks", "rsg_encode_hashed", "rsg_reconstruct_blocks",
 )
 
 # Staging bytes per sub-batch of rsg_encode_mixed_host (include/rsgpu.h)
@@ -81,6 +81,15 @@ class rsg_block(ctypes.Structure):
     _fields_ = [("shards", ctypes.POINTER(ctypes.c_void_p)),  # k+m host pointers, k data then m parity
                 ("shard_len", ctypes.c_uint64),
                 ("digests", ctypes.c_void_p)]                 # (k+m)*32 bytes, or NULL
+
+
+class rsg_rblock(ctypes.Structure):
+    """rsg_rblock (include/rsgpu.h): one degraded block of rsg_reconstruct_blocks."""
+    _fields_ = [("shards", ctypes.POINTER(ctypes.c_void_p)),  # k+m host pointers, every one a shard_len buffer
+                ("shard_len", ctypes.c_uint64),
+                ("present", ctypes.c_void_p),                 # k+m bytes
+                ("digests", ctypes.c_void_p),                 # expected (k+m)*32 bytes, or NULL
+                ("bad", ctypes.c_void_p)]                     # k+m bytes out, or NULL
 
 
 # rsg_stripe_desc (include/rsgpu.h): three little-endian u64 per stripe; a
@@ -181,6 +190,7 @@ def load():
         L.rsg_bitrot_verify_mixed_host.argtypes = [P, I, I, P, S, P, P]
         L.rsg_encode_blocks.argtypes = [P, I, I, S, P, I]
         L.rsg_encode_hashed.argtypes = [P, I, I, S, P, P, I]
+        L.rsg_reconstruct_blocks.argtypes = [P, I, I, S, P, I, I, P]
         _lib = L
         return L
 

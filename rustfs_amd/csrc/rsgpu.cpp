@@ -26,6 +26,7 @@
 
 #include "../../include/rsgpu.h"
 #include "rs_blocks.h"
+#include "rs_blocks_decode.h"
 #include "rs_kernels.h"
 #include "rs_mixed.h"
 
@@ -579,7 +580,10 @@ struct BlockSlot {
     uint8_t* h = nullptr;  // kBlockTableBytes of tables, then kBlockDigestBytes of digests
     bool busy = false;
 };
-constexpr size_t kBlockTableBytes = (size_t)rsg::blocks::table_bytes_max(rsg::blocks::kMaxC, rsg::blocks::kMaxR);
+// (the gathered block reconstruct, rsg_reconstruct_blocks, runs on the same
+// slots: its tables are the larger)
+constexpr size_t kBlockTableBytes = (size_t)std::max(rsg::blocks::table_bytes_max(rsg::blocks::kMaxC, rsg::blocks::kMaxR),
+                                                     rsg::blocks::rtable_bytes_max());
 constexpr size_t kBlockDigestBytes = rsg::blocks::kMaxBatchBlocks * (size_t)(rsg::blocks::kMaxC + rsg::blocks::kMaxR) * 32;
 
 constexpr int kBlockSlots = 4;  // batches in flight: a process has 4 hardware queues
@@ -3588,6 +3592,192 @@ int rsg_hash(rsg_ctx* ctx, int algo, const uint8_t* data, size_t len, uint8_t ou
     if ((st = hash_messages(algo, d, len, 1, 1, 0, 0, d + data_bytes, s))) return st;
     if ((st = hip_status(hipMemcpyAsync(out, d + data_bytes, 32, hipMemcpyDeviceToHost, s)))) return st;
     return hip_status(hipStreamSynchronize(s));
+}
+
+}  // extern "C"
+
+// ---- gathered block reconstruct (rs_blocks_decode_plan.h, rs_blocks_decode.hip) ----
+
+namespace {
+
+static_assert(sizeof(rsg_rblock) == sizeof(bk::RBlock) && offsetof(rsg_rblock, shard_len) == offsetof(bk::RBlock, shard_len) &&
+                  offsetof(rsg_rblock, present) == offsetof(bk::RBlock, present) &&
+                  offsetof(rsg_rblock, digests) == offsetof(bk::RBlock, digests) &&
+                  offsetof(rsg_rblock, bad) == offsetof(bk::RBlock, bad),
+              "rsg_rblock is the planner's RBlock");
+
+int rblocks_verdict_status(bk::RVerdict v) {
+    return v == bk::kROk ? RSG_OK : v == bk::kREmpty ? RSG_ERR_EMPTY_SHARD : v == bk::kRTooFew ? RSG_ERR_TOO_FEW_SHARDS : RSG_ERR_INVALID_ARG;
+}
+
+// One block through the per-block path: rsg_hash's digest launch per present
+// shard, then rsg_reconstruct over the shards that passed.
+int run_rblock_alone(rsg_ctx* ctx, int k, int m, const bk::RBlock& b, int mode, int algo, int* status) {
+    const int t = k + m;
+    std::vector<uint8_t> usable((size_t)t);
+    int n_usable = 0;
+    for (int s = 0; s < t; ++s) {
+        usable[s] = b.present[s] ? 1 : 0;
+        if (usable[s] && bk::verified(b, algo != RSG_HASH_NONE)) {
+            uint8_t dg[32];
+            if (int st = rsg_hash(ctx, algo, b.shards[s], (size_t)b.shard_len, dg)) return st;
+            if (std::memcmp(dg, b.digests + 32 * (size_t)s, 32)) {
+                usable[s] = 0;
+                if (b.bad) b.bad[s] = 1;
+            }
+        }
+        n_usable += usable[s];
+    }
+    if (n_usable < k) {
+        if (status) *status = RSG_ERR_TOO_FEW_SHARDS;
+        return RSG_OK;
+    }
+    return rsg_reconstruct(ctx, k, m, (size_t)b.shard_len, b.shards, usable.data(), mode);
+}
+
+// One sub-batch that fits the stage, on a slot's stream: copies up, with
+// verification the hash launch, the digests back and a wait; then the plan of
+// the effective present sets, its tables up, the one reconstruct launch, the
+// copies down and the wait.
+int run_rblock_batch(rsg_ctx* ctx, Codec& cd, const bk::RBlock* b, size_t n, int mode, int algo, int* status) {
+    const int k = cd.k, m = cd.m, t = k + m;
+    std::vector<uint64_t> view(n * (size_t)t, 0);
+    if (zero_copy_enabled()) {
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t len = b[i].shard_len;
+            for (int s0 = 0; s0 < t;) {
+                int s1 = s0 + 1;
+                while (s1 < t && b[i].shards[s1] == b[i].shards[s1 - 1] + len) ++s1;
+                if (const uint8_t* dv = pinned_view(b[i].shards[s0], (size_t)(len * (uint64_t)(s1 - s0)), ctx->device))
+                    for (int s = s0; s < s1; ++s) view[i * (size_t)t + s] = (uint64_t)(uintptr_t)(dv + (uint64_t)(s - s0) * len);
+                s0 = s1;
+            }
+        }
+    }
+    int st = RSG_OK;
+    BlockSlot* slot = take_block_slot(ctx, &st);
+    if (!slot) return st;
+    hipStream_t s = slot->stream;
+    uint8_t* const d_tab = slot->d + RSG_BLOCKS_STAGE_BYTES;
+    uint8_t* const h_dig = slot->h + kBlockTableBytes;
+    bk::RLayout L;
+    bk::layout_r(k, m, n, b, algo != RSG_HASH_NONE, mode, view.data(), (uint64_t)(uintptr_t)slot->d, L);
+    if (L.stage_bytes > RSG_BLOCKS_STAGE_BYTES || L.digest_bytes > kBlockDigestBytes ||
+        L.unit.size() * sizeof(bk::HashUnit) > kBlockTableBytes)
+        st = RSG_ERR_INVALID_ARG;  // split_r() keeps all three
+    for (size_t c = 0; c < L.up.size() && !st; ++c)
+        st = hip_status(hipMemcpyAsync((void*)(uintptr_t)L.up[c].dev, L.up[c].host, (size_t)L.up[c].bytes, hipMemcpyHostToDevice, s));
+    std::vector<uint32_t> mask(n);
+    if (!st && !L.unit.empty()) {
+        std::memcpy(slot->h, L.unit.data(), L.unit.size() * sizeof(bk::HashUnit));
+        st = hip_status(hipMemcpyAsync(d_tab, slot->h, L.unit.size() * sizeof(bk::HashUnit), hipMemcpyHostToDevice, s));
+        if (!st) {
+            rsg::HashBlocksParams h;
+            h.unit = (const bk::HashUnit*)d_tab;
+            h.n = L.unit.size();
+            std::memcpy(h.key, hash_key(algo), sizeof(h.key));
+            st = hip_status(rsg::launch_hash_blocks(h, s));
+        }
+        if (!st)
+            st = hip_status(hipMemcpyAsync(h_dig, (const void*)(uintptr_t)L.digest_dev, (size_t)L.digest_bytes, hipMemcpyDeviceToHost, s));
+        const int sst = hip_status(hipStreamSynchronize(s));
+        if (!st) st = sst;
+    }
+    if (!st) {
+        // a present shard whose digest differs from its entry is rotten: marked, and unusable from here on
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t mk = bk::mask_of(t, b[i].present, nullptr);
+            for (int x = 0; x < t; ++x) {
+                const uint32_t at = L.digest_at[i * (size_t)t + x];
+                if (at != UINT32_MAX && std::memcmp(h_dig + at, b[i].digests + 32 * (size_t)x, 32)) {
+                    mk &= ~(1u << x);
+                    if (b[i].bad) b[i].bad[x] = 1;
+                }
+            }
+            mask[i] = mk;
+        }
+        bk::RPlan p;
+        bk::plan_r(k, m, n, b, mode, mask.data(), view.data(), L, p);
+        for (size_t i = 0; i < n; ++i)
+            if (p.too_few[i] && status) status[i] = RSG_ERR_TOO_FEW_SHARDS;
+        const bk::RTableLayout lay = bk::rtable_layout(k, L, p);
+        if (lay.bytes > kBlockTableBytes) st = RSG_ERR_INVALID_ARG;
+        if (!st && !p.desc.empty()) {
+            std::memcpy(slot->h + lay.desc_off, p.desc.data(), p.desc.size() * sizeof(bk::RDesc));
+            std::memcpy(slot->h + lay.tile_off, p.tile0.data(), p.tile0.size() * sizeof(uint32_t));
+            // every pattern's target rows over its survivors
+            uint32_t* const tabs = (uint32_t*)(slot->h + lay.tab_off);
+            const size_t tab_words = (size_t)(bk::rtab_bytes(k) / sizeof(uint32_t));
+            std::memset(tabs, 0, p.pat_mask.size() * tab_words * sizeof(uint32_t));
+            std::vector<uint8_t> present((size_t)t);
+            for (size_t q = 0; q < p.pat_mask.size() && !st; ++q) {
+                for (int x = 0; x < t; ++x) present[x] = p.pat_mask[q] >> x & 1u;
+                auto plan = cd.plan(present.data());
+                if (!plan) {
+                    st = RSG_ERR_INVALID_ARG;
+                    break;
+                }
+                const RowSet rs = reconstruct_rows(cd, *plan, present.data(), mode, 0);
+                if (rs.R > bk::kMaxR) {
+                    st = RSG_ERR_INVALID_ARG;  // never: at most m targets (targets_of)
+                    break;
+                }
+                for (int r = 0; r < rs.R; ++r)
+                    for (int c = 0; c < k; ++c) coef_tables(rs.coef[(size_t)r * k + c], tabs + q * tab_words + ((size_t)r * k + c) * 5);
+            }
+            if (!st)
+                st = hip_status(hipMemcpyAsync(d_tab + lay.desc_off, slot->h + lay.desc_off, (size_t)(lay.bytes - lay.desc_off), hipMemcpyHostToDevice, s));
+            if (!st) {
+                rsg::ReconBlocksParams r;
+                r.desc = (const bk::RDesc*)(d_tab + lay.desc_off);
+                r.tile0 = (const uint32_t*)(d_tab + lay.tile_off);
+                r.tab = (const uint32_t*)(d_tab + lay.tab_off);
+                r.n = (uint32_t)p.desc.size();
+                r.C = (uint32_t)k;
+                st = hip_status(rsg::launch_reconstruct_blocks(r, p.tile0.back(), s));
+            }
+            for (size_t c = 0; c < p.down.size() && !st; ++c)
+                st = hip_status(hipMemcpyAsync(p.down[c].host, (const void*)(uintptr_t)p.down[c].dev, (size_t)p.down[c].bytes, hipMemcpyDeviceToHost, s));
+        }
+    }
+    // nothing queued may outlive the call, whatever failed
+    const int sst = hip_status(hipStreamSynchronize(s));
+    if (!st) st = sst;
+    give_block_slot(ctx, slot);
+    return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsg_reconstruct_blocks(rsg_ctx* ctx, int k, int m, size_t n, const rsg_rblock* blocks, int mode, int algo, int* status) {
+    int st = enter(ctx);
+    if (st) return st;
+    if ((st = check_geometry(k, m))) return st;
+    if (n == 0) return RSG_OK;
+    const bk::RBlock* b = (const bk::RBlock*)blocks;
+    if ((st = rblocks_verdict_status(bk::validate_r(k, m, n, b, mode, algo, status != nullptr)))) return st;
+    for (size_t i = 0; i < n; ++i) {
+        if (b[i].bad) std::memset(b[i].bad, 0, (size_t)(k + m));
+        if (status) status[i] = RSG_OK;
+    }
+    if (m == 0) return RSG_OK;
+    if (!bk::kernel_geometry(k, m)) {
+        for (size_t i = 0; i < n && !st; ++i) st = run_rblock_alone(ctx, k, m, b[i], mode, algo, status ? status + i : nullptr);
+        return st;
+    }
+    auto cd = get_codec(k, m);
+    if (!cd) return RSG_ERR_INVALID_ARG;
+    std::vector<bk::SubBatch> subs;
+    bk::split_r(k, m, n, b, algo != RSG_HASH_NONE, RSG_BLOCKS_STAGE_BYTES, subs);
+    for (const bk::SubBatch& sb : subs) {
+        int* const sub_status = status ? status + sb.first : nullptr;
+        st = sb.alone ? run_rblock_alone(ctx, k, m, b[sb.first], mode, algo, sub_status)
+                      : run_rblock_batch(ctx, *cd, b + sb.first, sb.count, mode, algo, sub_status);
+        if (st) break;
+    }
+    return st;
 }
 
 }  // extern "C"

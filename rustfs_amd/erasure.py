@@ -456,6 +456,65 @@ class Erasure:
                                             ctypes.byref(descs), algo if digests is not None else _lib.RSG_HASH_NONE),
               "Reed-Solomon encode failed")
 
+    def decode_blocks(self, blocks: Sequence[List], digests: Optional[Sequence] = None,
+                      mode: int = _lib.RSG_RECONSTRUCT_DATA, algo: int = _lib.RSG_HASH_HIGHWAY256S) -> list:
+        """Rebuild n unrelated degraded blocks in one call
+        (rsg_reconstruct_blocks): blocks[i] is a list of k+m uint8 buffers of
+        one length (its own) or None for a shard that was not read, as
+        ReedSolomonEncoder's reconstruct calls take them; the shards the mode
+        fills are allocated in the list (parity stays None under
+        RSG_RECONSTRUCT_DATA).  digests, if given, holds per block the
+        expected (k+m, 32) uint8 digests or None: a present shard that does
+        not hash to its entry is treated as not read and rebuilt in place if
+        the mode rebuilds it.  Returns per block (status, bad): RSG_OK or
+        RSG_ERR_TOO_FEW_SHARDS (nothing of that block written), and a (k+m,)
+        uint8 array with 1 at every shard found rotten.  Raises only for
+        errors of the whole call."""
+        t, k = self.total_shard_count(), self.data_shards
+        if digests is not None and len(digests) != len(blocks):
+            raise TypeError("digests must hold one entry (an array or None) per block")
+        n = len(blocks)
+        descs = (_lib.rsg_rblock * max(n, 1))()
+        status = (ctypes.c_int * max(n, 1))()
+        bad = np.zeros((n, t), dtype=np.uint8)
+        keep = []
+        for i, shards in enumerate(blocks):
+            if len(shards) != t:
+                raise RsgError(_lib.RSG_ERR_INVALID_SHARD_COUNT, f"invalid shard count: got {len(shards)}, expected {t}")
+            lens = {_shard_view(s).size for s in shards if s is not None}
+            if len(lens) > 1:
+                raise RsgError(_lib.RSG_ERR_INCONSISTENT_LENGTH, "Reed-Solomon reconstruct failed")
+            size = lens.pop() if lens else 0
+            dg = digests[i] if digests is not None else None
+            if dg is not None:
+                dg = np.ascontiguousarray(_shard_view(dg))
+                if dg.size != t * 32:
+                    raise TypeError("a block's digests must hold (k+m, 32) bytes")
+            present = np.array([s is not None for s in shards], dtype=np.uint8)
+            arrs = []
+            for j, s in enumerate(shards):
+                if s is None:
+                    s = bytearray(size)  # Option::None -> freshly allocated Vec (filled by the codec)
+                    if j < k or mode != _lib.RSG_RECONSTRUCT_DATA:
+                        shards[j] = s
+                elif not _as_array(s).flags.writeable and (
+                        dg is not None or (j >= k and mode == _lib.RSG_RECONSTRUCT_REENCODE_PARITY)):
+                    # a rebuilt rotten shard, or re-encoded parity, replaces the present buffer
+                    s = bytearray(s)
+                    shards[j] = s
+                arrs.append(_shard_view(s))
+            ptrs = _ptrs(arrs)
+            keep.append((arrs, ptrs, dg, present))
+            descs[i].shards = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
+            descs[i].shard_len = size
+            descs[i].present = present.ctypes.data
+            descs[i].digests = dg.ctypes.data if dg is not None else None
+            descs[i].bad = bad[i].ctypes.data
+        check(_lib.load().rsg_reconstruct_blocks(_lib.context(self._device).handle, k, self.parity_shards, n,
+                                                 ctypes.byref(descs), mode, algo if digests is not None else _lib.RSG_HASH_NONE,
+                                                 status), "Reed-Solomon reconstruct failed")
+        return [(st, bad[i]) for i, st in enumerate(_lib.status_list(status, n))]
+
     # -- mixed-length batches: every stripe its own shard length (rsg_encode_mixed_*) --
     def _mixed_desc(self, desc, data_len: int, parity_len: int, digests_len: Optional[int]) -> np.ndarray:
         """The (n, 3) uint64 descriptor array [data_off, parity_off, shard_len]
