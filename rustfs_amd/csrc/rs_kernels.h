@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rs_verify_pick.h"
+
 namespace rsg {
 
 constexpr int kMaxC = 16;  // inputs per launch (more are chained with GF_MODE_XOR)
@@ -96,11 +98,18 @@ struct HashParams {
     uint8_t* out;            // digests (may be null in verify mode)
     uint64_t out_stride;     // bytes between digests j and j+1 (0 = 32: packed)
     // verify mode (expect != null): compare with the stored digest of message j
-    // at expect + j*expect_stride and clear flags[j] on mismatch.  Callers set
-    // every flag to 1 first: a multi-file verify that launch_hh256 hands to the
-    // DMA-ring walk (launch_verify_records_dma, rs_verify.hip) writes each
-    // flag whole (1 verified, 0 not), so a flag pre-cleared by the caller is
-    // not kept
+    // at expect + j*expect_stride.  Two flag contracts, by the kernel family
+    // launch_hh256 picks (rs_verify_pick.h):
+    //  - k_hh256_quad only clears: flags[j] = 0 on a mismatch, untouched on a
+    //    match.  The caller sets every flag of the launch to 1 first; the flags
+    //    live in pooled scratch that the next call reuses, so a launch without
+    //    that fill reads an earlier call's verdicts.
+    //  - the DMA-ring walk (launch_verify_records_dma, rs_verify.hip) writes
+    //    each record's flag whole (1 verified, 0 not), whatever it held: a flag
+    //    pre-cleared by the caller is not kept.
+    // Callers cannot tell which family a launch takes, so they fill with 1
+    // and rely on neither a kept 0 nor an unwritten flag
+    // (tests/test_gpu_verify_walks.py test_no_memory_between_calls)
     const uint8_t* expect;
     uint64_t expect_stride;
     uint8_t* flags;
@@ -123,8 +132,9 @@ hipError_t launch_gf_apply_vec(GfApplyParams p, uint64_t n_stripes, hipStream_t 
 hipError_t launch_gf_apply_byte(GfApplyParams p, uint64_t n_stripes, hipStream_t stream);
 hipError_t launch_hh256(const HashParams& p, hipStream_t stream);
 // A multi-file verify of records at unaligned pitches on the LDS-DMA ring
-// (rs_verify.hip); false: not taken, launch_hh256 runs the quad kernel.
-bool launch_verify_records_dma(const HashParams& h, hipStream_t stream);
+// (rs_verify.hip), as pick_hash_launch chose it (rs_verify_pick.h); false:
+// not a ring pick, nothing launched.
+bool launch_verify_records_dma(const HashParams& h, const HashPick& pick, hipStream_t stream);
 // n bytes of device memory to page-locked host memory (dst = its device
 // view), as a kernel on the stream; 16-byte aligned ends.
 hipError_t launch_copy_to_host(uint8_t* dst, const uint8_t* src, uint64_t n, hipStream_t stream);

@@ -1450,38 +1450,46 @@ hipError_t launch_copy_to_host(uint8_t* dst, const uint8_t* src, uint64_t n, hip
     return hipGetLastError();
 }
 
+// The launch's shape as the kernel choice reads it (rs_verify_pick.h).
+static HashPickIn hash_pick_in(const HashParams& p, const Tuning& t) {
+    static_assert(kPickMaxBases == kMaxHashBases, "the pick sees every file of a launch");
+    HashPickIn in = {};
+    in.n = p.n;
+    in.nbases = p.nbases;
+    in.per_base = p.per_base;
+    in.len = p.len;
+    in.stripe_stride = p.stripe_stride;
+    in.digest_off = p.digest_off;
+    in.flags = p.flags != nullptr;
+    in.data = (uint64_t)(uintptr_t)p.data;
+    in.shard_pitch = p.shard_pitch;
+    for (uint32_t b = 0; b < p.nbases && b < (uint32_t)kMaxHashBases; ++b) {
+        in.base[b] = (uint64_t)(uintptr_t)p.base[b];
+        in.has_copy[b] = p.copy_base[b] != nullptr;
+        in.has_flag[b] = p.flag_base[b] != nullptr;
+    }
+    in.depth = t.hash_depth;
+    in.unal = t.hash_unal;
+    in.direct_copy = t.hash_direct_copy;
+    return in;
+}
+
 hipError_t launch_hh256(const HashParams& p, hipStream_t stream) {
-    if (p.n == 0) return hipSuccess;
-    const uint64_t blocks = (p.n * 4u + 255u) / 256u;  // one quad per message
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    bool copy = false;  // copy mode when any file of the launch has a copy target
-    for (uint32_t b = 0; b < p.nbases; ++b) copy = copy || p.copy_base[b];
-    if (!copy && launch_verify_records_dma(p, stream)) return hipGetLastError();
-    // copy mode: staged 16-byte stores (COPY = 2) by default (Tuning:
-    // direct 8-byte stores for A/B runs); 8-packet batches in flight per
-    // lane: 2 by default
     const Tuning& t = tuning();  // one snapshot for the whole launch
-    const bool direct_copy = t.hash_direct_copy;
-    const int depth = t.hash_depth;
+    const HashPick pick = pick_hash_launch(hash_pick_in(p, t));  // which kernel and why: rs_verify_pick.h
+    if (pick.kind == kPickNone) return hipSuccess;
+    if (pick.kind == kPickInvalid) return hipErrorInvalidValue;
+    if (pick.kind == kPickRing) {
+        return launch_verify_records_dma(p, pick, stream) ? hipGetLastError() : hipErrorInvalidValue;
+    }
     using HashKernel = void (*)(const HashParams);
     HashKernel k;
-    // messages at odd offsets (record pitch 174795 of RS(6,4) at 1 MiB
-    // blocks): aligned loads and a funnel shift, 1.005 -> 0.899 ms for the
-    // all-present GET; at even offsets (RS(10,4), RS(12,4): 2 mod 8) the
-    // hardware's unaligned loads are 4-5 % faster than the funnel
-    // (profiles/r04/o/).  Tuning::hash_unal, RSG_HASH_UNAL=0: always the loads.
-    bool even = true;
-    if (p.nbases) {
-        even = p.stripe_stride % 2 == 0;
-        for (uint32_t b = 0; b < p.nbases; ++b) even = even && (uintptr_t)p.base[b] % 2 == 0;
-    } else {
-        even = (uintptr_t)p.data % 2 == 0 && p.stripe_stride % 2 == 0 && p.shard_pitch % 2 == 0;
-    }
-    if (!copy && depth == 2 && !even && t.hash_unal) k = k_hh256_quad<0, 2, true>;
-    else if (!copy) k = depth == 1 ? k_hh256_quad<0, 1> : depth == 2 ? k_hh256_quad<0, 2> : k_hh256_quad<0, 3>;
-    else if (direct_copy) k = depth == 1 ? k_hh256_quad<1, 1> : depth == 2 ? k_hh256_quad<1, 2> : k_hh256_quad<1, 3>;
+    const int depth = pick.depth;
+    if (pick.unal) k = k_hh256_quad<0, 2, true>;
+    else if (pick.copy == 0) k = depth == 1 ? k_hh256_quad<0, 1> : depth == 2 ? k_hh256_quad<0, 2> : k_hh256_quad<0, 3>;
+    else if (pick.copy == 1) k = depth == 1 ? k_hh256_quad<1, 1> : depth == 2 ? k_hh256_quad<1, 2> : k_hh256_quad<1, 3>;
     else k = depth == 1 ? k_hh256_quad<2, 1> : depth == 2 ? k_hh256_quad<2, 2> : k_hh256_quad<2, 3>;
-    hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(k, dim3((uint32_t)pick.blocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -19,10 +19,6 @@
 #include "rs_kernels.h"
 #include "rs_records.h"
 
-#ifndef RSG_VERIFY_DMA
-#define RSG_VERIFY_DMA 1  // 0: never (A/B builds)
-#endif
-
 namespace rsg {
 
 namespace {
@@ -30,12 +26,8 @@ namespace {
 constexpr int kVG = 4;  // records per file per workgroup
 
 // Up to 12 files: a 3-slot ring (two steps of DMA in flight), two workgroups
-// a CU; 13-15 files: a 2-slot ring (RS(10,4)'s 14 files 10 % faster than the
-// quad kernel; RS(12,4)'s 16, 1 % slower, stay on it).  Launches of 13-15
-// files at odd record pitches stay on the quad kernel's funnel (RS(14,2)'s 16:
-// 12 % slower on the ring), more files too; split launches of 8 + 8 files
-// measured 12-24 % slower than either, and 2-record workgroups on a 3-slot
-// ring past 12 files 12-30 % slower (profiles/r05/ab_verify/, g2/).
+// a CU; 13-15 files: a 2-slot ring.  Which launches come here, and the
+// measurements behind the thresholds: pick_verify_ring (rs_verify_pick.h).
 template <int NF>
 struct VerifyShape : RecRing<NF, kVG> {
     static constexpr int RD = NF <= 12 ? 3 : 2;
@@ -75,37 +67,26 @@ const VerifyLaunch kLaunch[kMaxRingFiles + 1] = {
 
 }  // namespace
 
-// A multi-file verify launch as launch_hh256 takes it (h.nbases files of
+static_assert(kPickStep == dma::CH && kPickRingRecords == kVG && kPickMaxRingFiles == kMaxRingFiles &&
+                  VerifyShape<12>::RD == 3 && VerifyShape<13>::RD == 2,
+              "rs_verify_pick.h describes these kernels");
+
+// A multi-file verify launch that pick_hash_launch (rs_verify_pick.h: which
+// file counts, pitches and alignments) gave to the DMA ring: h.nbases files of
 // h.per_base records at pitch h.stripe_stride, digest 32 bytes before each
-// body, flags per file and record, no copies): run on the DMA ring when the
-// records sit off 16-byte alignment (VerifyShape: which file counts and
-// pitches).  false: not taken (the caller launches k_hh256_quad).
-// The kernel writes each record's flag whole (1 verified, 0 not), where the
-// quad kernel only clears.
-bool launch_verify_records_dma(const HashParams& h, hipStream_t stream) {
-    if (!RSG_VERIFY_DMA || h.nbases < 1 || h.nbases > (uint32_t)kMaxRingFiles || h.digest_off != -32 ||
-        h.len == 0 || h.per_base == 0 || h.flags)
-        return false;
-    bool aligned = h.stripe_stride % 16 == 0;
-    for (uint32_t b = 0; b < h.nbases; ++b) {
-        if (h.copy_base[b] || !h.flag_base[b]) return false;
-        aligned = aligned && (uintptr_t)h.base[b] % 16 == 0;
-    }
-    if (aligned) return false;  // the quad kernel's loads are aligned: nothing to gain
-    bool odd = h.stripe_stride % 2 != 0;
-    for (uint32_t b = 0; b < h.nbases; ++b) odd = odd || (uintptr_t)h.base[b] % 2 != 0;
-    if (h.nbases > 12 && odd) return false;
-    const uint64_t steps = (h.len + dma::CH - 1) / dma::CH;
-    const uint64_t blocks = (h.per_base + kVG - 1) / kVG;
-    // per-lane DMA offsets are 32-bit: HS records and a body
-    if (steps > 0xffffffffull || blocks > 0x7fffffffull || 3 * h.stripe_stride >= (1ull << 32)) return false;
+// body, flags per file and record, no copies.  false: not a ring pick,
+// nothing launched.
+// The kernel writes each record's flag whole (1 verified, 0 not), whatever
+// the flag held before; the quad kernel only clears a flag its caller set to 1.
+bool launch_verify_records_dma(const HashParams& h, const HashPick& pick, hipStream_t stream) {
+    if (pick.kind != kPickRing || pick.nf != (int)h.nbases || pick.nf < 1 || pick.nf > kMaxRingFiles) return false;
     GfApplyParams p;
     memset(&p, 0, sizeof(p));
-    p.units = (uint32_t)steps;
+    p.units = pick.steps;
     p.wave_prio = 0;
     HashParams q = h;
     q.n = h.per_base;  // the ring's stripes: the records of each file
-    kLaunch[h.nbases](blocks, p, q, stream);
+    kLaunch[pick.nf](pick.blocks, p, q, stream);
     return true;
 }
 

@@ -1244,9 +1244,13 @@ int for_each_pattern_run(int t, uint64_t n, const std::vector<uint8_t>& flags, F
 }
 
 // Verify (and optionally gather) records of the shard files listed in `idx`
-// for stripes [lo, hi): flags[i*n + s] in device scratch is set to 1 for a
-// present shard and cleared by the kernel on a digest mismatch.  With d_out,
-// data shard i's record bodies are also copied to d_out + s*k*S + i*S.
+// for stripes [lo, hi): flags[i*n + s] in device scratch (pooled: it holds an
+// earlier call's verdicts) is set to 1 here for every listed shard; then the
+// launch's kernel either clears it on a digest mismatch and leaves it on a
+// match (k_hh256_quad) or writes it whole, 1 verified and 0 not (the DMA
+// ring): HashParams, rs_kernels.h.  Rows and stripes outside idx x [lo, hi)
+// are not touched.  With d_out, data shard i's record bodies are also copied
+// to d_out + s*k*S + i*S.
 int launch_verify_group(const std::vector<int>& idx, const uint8_t* const* d_files, uint8_t* d_flags, int k,
                         uint64_t shard_len, uint64_t n, uint64_t lo, uint64_t hi, const uint64_t* key,
                         uint8_t* d_out, hipStream_t s) {
